@@ -398,6 +398,32 @@ def _library_identity():
             "override": bool(override), "product_build": (not override) and stamp == _b.source_hash()}
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: the whole dump, every rank's files together, stays under 64 MB
+
+
+def dump_outputs(pf, outdir, rank, world):
+    """--dump-outputs DIR: what the last timed step left to its caller — the particles' states, their parents, their log-weights
+    (zero after the resample) and the log marginal likelihood estimate — as float64 DIR/<name>.npy, for comparing two builds output
+    for output.  At N > 1 each rank writes its own shard as rank<r>_<name>.npy and rank 0 the log-ML.  A population too large for the
+    budget is dumped at a fixed, seeded sample of particle indices (same sample every run), saved beside it as sample_index.npy."""
+    lml = pf.log_marginal_likelihood_estimate()   # (collective at N > 1: every rank asks)
+    arrays = {"states": pf.states(), "parents": pf.parents.astype(np.float64), "log_weights": pf.log_weights}
+    n = arrays["states"].shape[0]
+    per_particle = sum(a[0].nbytes for a in arrays.values())
+    budget = DUMP_BYTES // world - 4096   # (room for the .npy headers and the log-ML)
+    if n * per_particle > budget:
+        k = budget // (per_particle + 8)
+        idx = np.sort(np.random.default_rng(20241008).choice(n, size=k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    prefix = "" if world == 1 else f"rank{rank}_"
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    if rank == 0:
+        np.save(os.path.join(outdir, "log_ml.npy"), np.array([lml], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -409,7 +435,10 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not record hipEvents around each launch in the timed region")
     ap.add_argument("--no-sub-benches", action="store_true", help="skip the c3 / c4 / c5 sub-objects")
     ap.add_argument("--no-systematic-leg", action="store_true", help="skip the supplementary systematic-resampling leg (profiles: only the headline step's kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed regions, write what the last timed step computed as DIR/<name>.npy (float64, < 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -559,6 +588,8 @@ def main():
         d, ev = timed_region()
         dts.append(d); evs.append(ev)
     dt = float(np.median(dts))
+    if args.dump_outputs:   # (before the supplementary legs below move the filter on)
+        dump_outputs(pf, args.dump_outputs, rank, world)
     # ---- supplementary: the same K steps with systematic resampling (named next to multinomial in the north star; not `value`)
     dt_sys = None
     if not args.no_systematic_leg:   # (at N > 1 too: the sharded filter's lattice schemes need no enumeration of all N draws)

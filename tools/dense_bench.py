@@ -1,5 +1,5 @@
 import sys, json, time, os
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import bench
 r = bench.sub_benches(20, 3, ("c5",))

@@ -1,5 +1,5 @@
-import sys, ctypes as C, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, ctypes as C, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from modppl_amd import capi
 import math
 L = capi.load()
