@@ -30,6 +30,16 @@ int32_t mp_probe_u01(uint64_t seed, uint32_t slot0, uint32_t step, uint32_t doma
  * eigen transform, :30-33).  chain = 0: the reference's multiply-then-add order; 1: the matrix cores' fma chain. */
 int32_t mp_probe_mvnormal(int32_t k, int32_t chain, const double* x, const double* mu, const double* cov, int64_t n, double* logpdf_out,
                           uint64_t seed, uint32_t slot0, uint32_t step, uint32_t domain, uint32_t site, double* sample_out, int32_t device);
+/* The count and positive-real distributions of modppl_amd/csrc/mp_dists.h (counts are doubles):
+ *   dist  MP_PROBE_DIST_POISSON (p0 = rate), _GAMMA (p0 = shape, p1 = scale), _BETA (p0 = a, p1 = b), _GEOMETRIC (p0 = p),
+ *         _UNIFORM_DISCRETE (p0 = a, p1 = b, inclusive); op 0 only: _LGAMMA, _LOG1P (mp_math.h, of x)
+ *   op 0  out[i] = logpdf(x[i]; p0[i], p1[i])
+ *   op 1  out[i] = a sample with parameters (p0[i], p1[i]) from the Philox stream (seed, slot0 + i, step, domain, site); x unused
+ * p0 / p1 may be NULL (zeros) where a distribution has fewer parameters. */
+enum mp_probe_dist_kind { MP_PROBE_DIST_POISSON = 0, MP_PROBE_DIST_GAMMA = 1, MP_PROBE_DIST_BETA = 2, MP_PROBE_DIST_GEOMETRIC = 3,
+                          MP_PROBE_DIST_UNIFORM_DISCRETE = 4, MP_PROBE_DIST_LGAMMA = 5, MP_PROBE_DIST_LOG1P = 6 };
+int32_t mp_probe_dist(int32_t dist, int32_t op, const double* x, const double* p0, const double* p1, int64_t n, uint64_t seed, uint32_t slot0,
+                      uint32_t step, uint32_t domain, uint32_t site, double* out, int32_t device);
 /* One v_mfma_f64_16x16x4_f64 on one wave: D = A * B + C (row-major A[16][4], B[4][16], C, D[16][16]): pins the matrix
  * core's accumulation order, which the dense-transition kernels and the CPU checker's canonical matvec restate. */
 int32_t mp_probe_mfma_f64(const double* A16x4, const double* B4x16, const double* C16x16, double* D16x16, int32_t device);

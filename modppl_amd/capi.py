@@ -44,7 +44,7 @@ SYMBOLS = [
     "mp_mh_create_fn", "mp_mh_n_sites", "mp_mh_read_trace", "mp_fn_update", "mp_fn_regenerate", "mp_fn_assess", "mp_fn_propose",
     "mp_fn_generate", "mp_fn_simulate", "mp_fn_generate_create", "mp_fn_simulate_create", "mp_fn_importance_sampling", "mp_fn_importance_resampling",
     # include/modppl_hip_probe.h
-    "mp_probe_math", "mp_probe_normal_sample", "mp_probe_u01", "mp_probe_mfma_f64", "mp_probe_mvnormal",
+    "mp_probe_math", "mp_probe_normal_sample", "mp_probe_u01", "mp_probe_mfma_f64", "mp_probe_mvnormal", "mp_probe_dist",
 ]
 
 
@@ -214,6 +214,7 @@ def _load_so(so):
     L.mp_probe_u01.argtypes = [u64, u32, u32, u32, u32, u32, i64, dp, i32]
     L.mp_probe_mfma_f64.argtypes = [dp, dp, dp, dp, i32]
     L.mp_probe_mvnormal.argtypes = [i32, i32, dp, dp, dp, i64, dp, u64, u32, u32, u32, u32, dp, i32]
+    L.mp_probe_dist.argtypes = [i32, i32, dp, dp, dp, i64, u64, u32, u32, u32, u32, dp, i32]
     return L
 
 

@@ -159,3 +159,148 @@ MP_HD int mp_categorical_sample(mp_site& st, const double* probs, int n) {
     const mp_u64x2 blk = st.next_block();
     return mp_categorical_scan(mp_u01(blk.a), probs, n);
 }
+
+// ---- counts and positive reals: poisson, gamma, beta, geometric, uniform_discrete ------------------------------------------
+//   poisson          modppl/src/modeling/dists/poisson.rs    rate r > 0                 k = 0, 1, ...
+//   gamma            modppl/src/modeling/dists/gamma.rs      shape a > 0, SCALE b > 0   x > 0
+//   beta             modppl/src/modeling/dists/beta.rs       a, b > 0                   0 < x < 1
+//   geometric        modppl/src/modeling/dists/geometric.rs  0 < p < 1                  k = 0, 1, ... (failures before the first success)
+//   uniform_discrete modppl/src/modeling/dists/uniform.rs    integers a <= b            a, ..., b
+// Integer values travel as doubles (as bernoulli's 0 / 1 do).  Log-densities: a value outside the support (a negative or non-integer
+// count, x <= 0, ...) is -inf; parameters outside the ranges above give NaN.  The reference's log-factorials (a sum of logs) and
+// gamma-function ratios become mp_lgamma; log(1 - p) is mp_log1p(-p).
+// Samplers draw whole Philox blocks from their own site's stream (mp_site), one after the other: how many attempts a rejection
+// sampler needs changes no other site's draws.  Continuous samples lie strictly inside the support: an underflowed gamma or beta
+// variate is clamped to the smallest positive normal double, a beta variate that rounds to 1 to 1 - 2^-53.
+#include "mp_binomial.h"   // mp_stirling_tail
+
+#define MP_NAN (mp_u2f(0x7FF8000000000000ull))
+#define MP_MIN_NORMAL 0x1p-1022
+#define MP_ONE_MINUS_ULP 0x1.fffffffffffffp-1   // 1 - 2^-53, the largest double below 1
+constexpr uint32_t MP_DIST_MAX_ATTEMPTS = 256u; // rejection samplers: acceptance >= 0.6 per attempt, so never reached in practice
+
+// a count: a finite, non-negative integer
+MP_HD bool mp_is_count(double k) { return k >= 0. && k - floor(k) == 0.; }
+
+// poisson.rs:17-19: k ln r - r - ln k!; k = 0 gives -r (no 0 * ln r term: an underflowed rate of 0 scores a zero count as 0)
+MP_HD double mp_poisson_logpdf(double k, double r) {
+    if (!(r >= 0.)) return MP_NAN;
+    if (!mp_is_count(k) || r == MP_INF) return MP_NEG_INF;
+    if (k == 0.) return -r;
+    return k * mp_log(r) - r - mp_lgamma(k + 1.);
+}
+// r < 10: inversion by sequential search from 0 (one block; the search stops at 64, where the remaining mass is < 1e-30);
+// r >= 10: PTRS, the transformed rejection sampler with squeeze of W. Hoermann, "The transformed rejection method for generating
+// Poisson random variables", Insurance: Math. Econ. 12 (1993), restated from the published steps: attempt j takes block j as (U, V).
+// A rate of 0 gives 0; a negative, non-finite or >= 2^52 rate gives NaN.
+MP_HD double mp_poisson_sample(mp_site& st, double r) {
+    if (!(r >= 0.) || !(r < 0x1p52)) return MP_NAN;
+    if (r < 10.) {
+        const double u = mp_u01(st.next_block().a);
+        double p = mp_exp(-r), F = p, k = 0.;
+        while (u > F && k < 64.) {
+            k += 1.;
+            p = p * r / k;
+            F += p;
+        }
+        return k;
+    }
+    const double slam = mp_sqrt(r), loglam = mp_log(r);
+    const double b = 0.931 + 2.53 * slam;
+    const double a = -0.059 + 0.02483 * b;
+    const double ln_inv_alpha = mp_log(1.1239 + 1.1328 / (b - 3.4));
+    const double vr = 0.9277 - 3.6224 / (b - 2.);
+    for (uint32_t att = 0; att < MP_DIST_MAX_ATTEMPTS; ++att) {
+        const mp_u64x2 blk = st.next_block();
+        const double U = mp_u01(blk.a) - 0.5;
+        const double V = mp_u01(blk.b);
+        const double us = 0.5 - fabs(U);
+        const double k = floor((2. * a / us + b) * U + r + 0.43);
+        if (us >= 0.07 && V <= vr) return k;                       // the squeeze: ~ 87 % of the attempts
+        if (k < 0. || (us < 0.013 && V > us)) continue;
+        // ln(V alpha^-1 / (a / us^2 + b)) <= k ln r - r - ln k!, ln k! by Stirling with its tabulated tail (mp_binomial.h)
+        const double lfact = 0.91893853320467274178 + (k + 0.5) * mp_log(k + 1.) - (k + 1.) + mp_stirling_tail(k);
+        if (mp_log(V) + ln_inv_alpha - mp_log(a / (us * us) + b) <= -r + k * loglam - lfact) return k;
+    }
+    return floor(r);
+}
+
+// gamma.rs:17-20 with the scale parameterisation: (a - 1) ln x - x / b - ln Gamma(a) - a ln b
+MP_HD double mp_gamma_logpdf(double x, double a, double b) {
+    if (!(a > 0.) || !(b > 0.) || a == MP_INF || b == MP_INF || x != x) return MP_NAN;
+    if (!(x > 0.) || x == MP_INF) return MP_NEG_INF;
+    return (a - 1.) * mp_log(x) - x / b - mp_lgamma(a) - a * mp_log(b);
+}
+// Gamma(d + 1/3, 1) for d + 1/3 >= 1: G. Marsaglia and W. W. Tsang, "A simple method for generating gamma variables", ACM TOMS 26
+// (2000).  An attempt takes one block for the normal deviate (the polar method's pair, mp_polar_attempt: a rejected pair ends the
+// attempt) and, when 1 + c x > 0, the next block's first half for the acceptance uniform.
+MP_HD double mp_gamma_mt(mp_site& st, double d) {
+    const double c = 1. / mp_sqrt(9. * d);
+    for (uint32_t att = 0; att < MP_DIST_MAX_ATTEMPTS; ++att) {
+        double pu, pr;
+        if (!mp_polar_attempt(st.next_block(), &pu, &pr)) continue;
+        const double x = mp_std_normal_from_pair(pu, pr);
+        double v = 1. + c * x;
+        if (!(v > 0.)) continue;
+        v = v * v * v;
+        const double u = mp_u01(st.next_block().a);
+        const double x2 = x * x;
+        if (u < 1. - 0.0331 * (x2 * x2)) return d * v;
+        if (mp_log(u) < 0.5 * x2 + d * (1. - v + mp_log(v))) return d * v;
+    }
+    return d;
+}
+// Gamma(a, 1): a >= 1 directly; a < 1 as Gamma(a + 1) U^(1/a), formed in log space (ln G + ln U / a, U = 1 - u01 in (0, 1]: the next
+// block after the ones of Gamma(a + 1)) so that U^(1/a) does not underflow on its own
+MP_HD double mp_gamma_std_sample(mp_site& st, double a) {
+    if (a >= 1.) return mp_gamma_mt(st, a - 1. / 3.);
+    const double g = mp_gamma_mt(st, (a + 1.) - 1. / 3.);
+    const double lu = mp_log(1. - mp_u01(st.next_block().a));
+    return mp_exp(mp_log(g) + lu / a);
+}
+MP_HD double mp_gamma_sample(mp_site& st, double a, double b) {
+    if (!(a > 0.) || !(b > 0.) || a == MP_INF || b == MP_INF) return MP_NAN;
+    const double x = mp_gamma_std_sample(st, a) * b;
+    return x < MP_MIN_NORMAL ? MP_MIN_NORMAL : x;
+}
+
+// beta.rs:17-21, in log form: ln Gamma(a + b) - ln Gamma(a) - ln Gamma(b) + (a - 1) ln x + (b - 1) log1p(-x)
+MP_HD double mp_beta_logpdf(double x, double a, double b) {
+    if (!(a > 0.) || !(b > 0.) || a == MP_INF || b == MP_INF || x != x) return MP_NAN;
+    if (!(x > 0. && x < 1.)) return MP_NEG_INF;
+    return mp_lgamma(a + b) - mp_lgamma(a) - mp_lgamma(b) + (a - 1.) * mp_log(x) + (b - 1.) * mp_log1p(-x);
+}
+// X / (X + Y), X ~ Gamma(a, 1) then Y ~ Gamma(b, 1) from the same stream
+MP_HD double mp_beta_sample(mp_site& st, double a, double b) {
+    if (!(a > 0.) || !(b > 0.) || a == MP_INF || b == MP_INF) return MP_NAN;
+    const double X = mp_gamma_std_sample(st, a);
+    const double Y = mp_gamma_std_sample(st, b);
+    const double x = X / (X + Y);
+    return x < MP_MIN_NORMAL ? MP_MIN_NORMAL : (x < 1. ? x : MP_ONE_MINUS_ULP);
+}
+
+// geometric.rs:16-19: ln((1 - p)^k p) = k log1p(-p) + ln p
+MP_HD double mp_geometric_logpdf(double k, double p) {
+    if (!(p > 0. && p < 1.)) return MP_NAN;
+    if (!mp_is_count(k)) return MP_NEG_INF;
+    return k * mp_log1p(-p) + mp_log(p);
+}
+// inversion: floor(ln U / log1p(-p)), U = 1 - u01 in (0, 1] (P(k >= n) = P(U <= (1 - p)^n) = (1 - p)^n); + 0. turns U = 1's -0 into 0
+MP_HD double mp_geometric_sample(mp_site& st, double p) {
+    if (!(p > 0. && p < 1.)) return MP_NAN;
+    const double u = 1. - mp_u01(st.next_block().a);
+    return floor(mp_log(u) / mp_log1p(-p)) + 0.;
+}
+
+// uniform.rs:36-54, bounds inclusive: -ln(b - a + 1) on a, ..., b
+MP_HD bool mp_uniform_discrete_ok(double a, double b) { return a - floor(a) == 0. && b - floor(b) == 0. && a <= b; }
+MP_HD double mp_uniform_discrete_logpdf(double x, double a, double b) {
+    if (!mp_uniform_discrete_ok(a, b)) return MP_NAN;
+    return (a <= x && x <= b && x - floor(x) == 0.) ? -mp_log(b - a + 1.) : MP_NEG_INF;
+}
+// uniform.rs:48-52: trunc(u01 (b - a + 1)) + a (u01 (b - a + 1) >= 0: trunc = floor)
+MP_HD double mp_uniform_discrete_sample(mp_site& st, double a, double b) {
+    if (!mp_uniform_discrete_ok(a, b)) return MP_NAN;
+    const double x = floor(mp_u01(st.next_block().a) * (b - a + 1.)) + a;
+    return x > b ? b : x;
+}

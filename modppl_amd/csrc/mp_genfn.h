@@ -11,6 +11,8 @@
 //     g.template normal<SITE>(mu, sd, ln_sd)     `normal(mu, sd) %= addr`    -> sample_at (dyngenfn.rs:100-273)
 //     g.template bernoulli<SITE>(p)              `bernoulli(p) %= addr`
 //     g.template uniform<SITE>(a, b)             `uniform(a, b) %= addr`
+//     g.template poisson<SITE>(rate), gamma<SITE>(shape, scale), beta<SITE>(a, b), geometric<SITE>(p), uniform_discrete<SITE>(a, b)
+//                                                the count and positive-real distributions of mp_dists.h (a count is a double)
 //     g.template uniform_2d<SITE>(.., out), g.template mvnormal2<SITE>(mu, cov, .., out)   vector-valued sites: K = 2 consecutive slots
 //                                                SITE, SITE + 1 hold the value, SITE is the address (at_k)
 //     g.template call<SITES>(body)               `gen_fn(args) /= addr`      -> trace_at  (dyngenfn.rs:283-449);
@@ -113,6 +115,32 @@ struct mp_fn_uniform {
     double a, b;
     MP_HD double sample(mp_site& st) const { return mp_uniform_sample(st, a, b); }
     MP_HD double logpdf(double x) const { return mp_uniform_logpdf(x, a, b); }
+};
+// counts and positive reals (mp_dists.h); a count is a double holding an integer
+struct mp_fn_poisson {
+    double rate;
+    MP_HD double sample(mp_site& st) const { return mp_poisson_sample(st, rate); }
+    MP_HD double logpdf(double x) const { return mp_poisson_logpdf(x, rate); }
+};
+struct mp_fn_gamma {
+    double shape, scale;
+    MP_HD double sample(mp_site& st) const { return mp_gamma_sample(st, shape, scale); }
+    MP_HD double logpdf(double x) const { return mp_gamma_logpdf(x, shape, scale); }
+};
+struct mp_fn_beta {
+    double a, b;
+    MP_HD double sample(mp_site& st) const { return mp_beta_sample(st, a, b); }
+    MP_HD double logpdf(double x) const { return mp_beta_logpdf(x, a, b); }
+};
+struct mp_fn_geometric {
+    double p;
+    MP_HD double sample(mp_site& st) const { return mp_geometric_sample(st, p); }
+    MP_HD double logpdf(double x) const { return mp_geometric_logpdf(x, p); }
+};
+struct mp_fn_uniform_discrete {
+    double a, b;
+    MP_HD double sample(mp_site& st) const { return mp_uniform_discrete_sample(st, a, b); }
+    MP_HD double logpdf(double x) const { return mp_uniform_discrete_logpdf(x, a, b); }
 };
 
 // a scalar distribution as a one-value site
@@ -323,6 +351,16 @@ struct mp_fn_handler {
     MP_HD bool bernoulli(double p) { return at<SITE>(mp_fn_bernoulli{p}) != 0.; }
     template <int SITE>
     MP_HD double uniform(double a, double b) { return at<SITE>(mp_fn_uniform{a, b}); }
+    template <int SITE>
+    MP_HD double poisson(double rate) { return at<SITE>(mp_fn_poisson{rate}); }
+    template <int SITE>
+    MP_HD double gamma(double shape, double scale) { return at<SITE>(mp_fn_gamma{shape, scale}); }
+    template <int SITE>
+    MP_HD double beta(double a, double b) { return at<SITE>(mp_fn_beta{a, b}); }
+    template <int SITE>
+    MP_HD double geometric(double p) { return at<SITE>(mp_fn_geometric{p}); }
+    template <int SITE>
+    MP_HD double uniform_discrete(double a, double b) { return at<SITE>(mp_fn_uniform_discrete{a, b}); }
     // vector-valued sites (two slots each): `uniform_2d(bounds) %= addr`, `mvnormal(mu, cov) %= addr` with the covariance constants
     // hoisted by the functor (cov itself, row-major, is what a dynamic interpretation hands its own mvnormal)
     template <int SITE>

@@ -292,3 +292,168 @@ MP_HD double mp_atan2(double y, double x) {
     const double r = PI - (z - PI_LO);
     return yneg ? -r : r;
 }
+
+// ---------------------------------------------------------------------------------------
+// log1p / lgamma — same contract: one definition, IEEE ops only (+ - * / and integer bit work) plus mp_log, identical on host and
+// device.  The classical fdlibm schemes (s_log1p.c; e_lgamma_r.c for x > 0 only, so no sin and no reflection; Sun Microsystems
+// notice above applies), constants as published.  For the log-densities of mp_dists.h (poisson, gamma, beta, geometric).
+// ---------------------------------------------------------------------------------------
+// log(1 + x): x = -1 gives -inf, x < -1 NaN, +inf and NaN pass through
+MP_HD double mp_log1p(double x) {
+    const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
+    const double Lp1 = 6.666666666666735130e-01, Lp2 = 3.999999999940941908e-01, Lp3 = 2.857142874366239149e-01,
+                 Lp4 = 2.222219843214978396e-01, Lp5 = 1.818357216161805012e-01, Lp6 = 1.531383769920937332e-01,
+                 Lp7 = 1.479819860511658591e-01;
+    const uint64_t ux = mp_f2u(x);
+    const int32_t hx = (int32_t)(uint32_t)(ux >> 32);
+    const int32_t ax = hx & 0x7fffffff;
+    int k = 1, hu = 0;
+    double f = 0., c = 0.;
+    if (hx < 0x3FDA827A) {                            // x < 0.41422
+        if (ax >= 0x3ff00000) {                       // x <= -1
+            if (x == -1.0) return MP_NEG_INF;
+            return mp_u2f(0x7FF8000000000000ull);
+        }
+        if (ax < 0x3e200000) {                        // |x| < 2^-29
+            if (ax < 0x3c900000) return x;            // |x| < 2^-54
+            return x - x * x * 0.5;
+        }
+        if (hx > 0 || hx <= (int32_t)0xbfd2bec3u) {   // -0.2929 < x < 0.41422
+            k = 0; f = x; hu = 1;
+        }
+    }
+    if (hx >= 0x7ff00000) return x + x;               // +inf, NaN
+    if (k != 0) {
+        double u;
+        if (hx < 0x43400000) {
+            u = 1.0 + x;
+            hu = (int)(mp_f2u(u) >> 32);
+            k = (hu >> 20) - 1023;
+            c = (k > 0) ? 1.0 - (u - x) : x - (u - 1.0);   // the rounding error of 1 + x
+            c /= u;
+        } else {
+            u = x;
+            hu = (int)(mp_f2u(u) >> 32);
+            k = (hu >> 20) - 1023;
+            c = 0.;
+        }
+        hu &= 0x000fffff;
+        const uint64_t lo = mp_f2u(u) & 0xFFFFFFFFull;
+        if (hu < 0x6a09e) {
+            u = mp_u2f(((uint64_t)(uint32_t)(hu | 0x3ff00000) << 32) | lo);   // u in [1, sqrt 2)
+        } else {
+            k += 1;
+            u = mp_u2f(((uint64_t)(uint32_t)(hu | 0x3fe00000) << 32) | lo);   // u / 2 in [sqrt 2 / 2, 1)
+            hu = (0x00100000 - hu) >> 2;
+        }
+        f = u - 1.0;
+    }
+    const double hfsq = 0.5 * f * f;
+    const double dk = (double)k;
+    if (hu == 0) {                                    // |f| < 2^-20
+        if (f == 0.) {
+            if (k == 0) return 0.;
+            c += dk * LN2_LO;
+            return dk * LN2_HI + c;
+        }
+        const double R = hfsq * (1.0 - 0.66666666666666666 * f);
+        if (k == 0) return f - R;
+        return dk * LN2_HI - ((R - (dk * LN2_LO + c)) - f);
+    }
+    const double s = f / (2.0 + f);
+    const double z = s * s;
+    const double R = z * (Lp1 + z * (Lp2 + z * (Lp3 + z * (Lp4 + z * (Lp5 + z * (Lp6 + z * Lp7))))));
+    if (k == 0) return f - (hfsq - s * (hfsq + R));
+    return dk * LN2_HI - ((hfsq - (s * (hfsq + R) + (dk * LN2_LO + c))) - f);
+}
+
+// ln Gamma(x) for x > 0 (x <= 0 and NaN give NaN, +inf gives +inf).  mp_lgamma(1) = mp_lgamma(2) = 0 exactly.
+//   x < 2^-70: -log x;  x < 2: one of three expansions around the minimum tc = 1.4616.. or the zeros 1, 2 (x < 0.9 through
+//   lgamma(x + 1) - log x);  x < 8: the rational form on [2, 3) and log of the product of the shifts;  x < 2^58: Stirling's
+//   series;  beyond: x (log x - 1).
+MP_HD double mp_lgamma(double x) {
+    const double a0 = 7.72156649015328655494e-02, a1 = 3.22467033424113591611e-01, a2 = 6.73523010531292681824e-02,
+                 a3 = 2.05808084325167332806e-02, a4 = 7.38555086081402883957e-03, a5 = 2.89051383673415629091e-03,
+                 a6 = 1.19270763183362067845e-03, a7 = 5.10069792153511336608e-04, a8 = 2.20862790713908385557e-04,
+                 a9 = 1.08011567247583939954e-04, a10 = 2.52144565451257326939e-05, a11 = 4.48640949618915160150e-05;
+    const double tc = 1.46163214496836224576e+00, tf = -1.21486290535849611461e-01, tt = -3.63867699703950536541e-18;
+    const double t0 = 4.83836122723810047042e-01, t1 = -1.47587722994593911752e-01, t2 = 6.46249402391333854778e-02,
+                 t3 = -3.27885410759859649565e-02, t4 = 1.79706750811820387126e-02, t5 = -1.03142241298341437450e-02,
+                 t6 = 6.10053870246291332635e-03, t7 = -3.68452016781138256760e-03, t8 = 2.25964780900612472250e-03,
+                 t9 = -1.40346469989232843813e-03, t10 = 8.81081882437654011382e-04, t11 = -5.38595305356740546715e-04,
+                 t12 = 3.15632070903625950361e-04, t13 = -3.12754168375120860518e-04, t14 = 3.35529192635519073543e-04;
+    const double u0 = -7.72156649015328655494e-02, u1 = 6.32827064025093366517e-01, u2 = 1.45492250137234768737e+00,
+                 u3 = 9.77717527963372745603e-01, u4 = 2.28963728064692451092e-01, u5 = 1.33810918536787660377e-02;
+    const double v1 = 2.45597793713041134822e+00, v2 = 2.12848976379893395361e+00, v3 = 7.69285150456672783825e-01,
+                 v4 = 1.04222645593369134254e-01, v5 = 3.21709242282423911810e-03;
+    const double s0 = -7.72156649015328655494e-02, s1 = 2.14982415960608852501e-01, s2 = 3.25778796408930981787e-01,
+                 s3 = 1.46350472652464452805e-01, s4 = 2.66422703033638609560e-02, s5 = 1.84028451407337715652e-03,
+                 s6 = 3.19475326584100867617e-05;
+    const double r1 = 1.39200533467621045958e+00, r2 = 7.21935547567138069525e-01, r3 = 1.71933865632803078993e-01,
+                 r4 = 1.86459191715652901344e-02, r5 = 7.77942496381893596434e-04, r6 = 7.32668430744625636189e-06;
+    const double w0 = 4.18938533204672725052e-01, w1 = 8.33333333333329678849e-02, w2 = -2.77777777728775536470e-03,
+                 w3 = 7.93650558643019558500e-04, w4 = -5.95187557450339963135e-04, w5 = 8.36339918996282139126e-04,
+                 w6 = -1.63092934096575273989e-03;
+    if (!(x > 0.)) return mp_u2f(0x7FF8000000000000ull);   // x <= 0, NaN: outside the domain here
+    const uint64_t u = mp_f2u(x);
+    const uint32_t ix = (uint32_t)(u >> 32), lx = (uint32_t)u;
+    if (ix >= 0x7ff00000u) return x;                        // +inf
+    if (ix < 0x3b900000u) return -mp_log(x);                // x < 2^-70
+    if (((ix - 0x3ff00000u) | lx) == 0u || ((ix - 0x40000000u) | lx) == 0u) return 0.;   // x = 1, 2
+    double r;
+    if (ix < 0x40000000u) {                                 // x < 2
+        double y;
+        int i;
+        if (ix <= 0x3feccccc) {                             // x < 0.9: lgamma(x) = lgamma(x + 1) - log(x)
+            r = -mp_log(x);
+            if (ix >= 0x3FE76944u) { y = 1.0 - x; i = 0; }
+            else if (ix >= 0x3FCDA661u) { y = x - (tc - 1.0); i = 1; }
+            else { y = x; i = 2; }
+        } else {
+            r = 0.;
+            if (ix >= 0x3FFBB4C3u) { y = 2.0 - x; i = 0; }         // [1.7316, 2)
+            else if (ix >= 0x3FF3B4C4u) { y = x - tc; i = 1; }     // [1.23, 1.73)
+            else { y = x - 1.0; i = 2; }
+        }
+        if (i == 0) {
+            const double z = y * y;
+            const double p1 = a0 + z * (a2 + z * (a4 + z * (a6 + z * (a8 + z * a10))));
+            const double p2 = z * (a1 + z * (a3 + z * (a5 + z * (a7 + z * (a9 + z * a11)))));
+            const double p = y * p1 + p2;
+            r += (p - 0.5 * y);
+        } else if (i == 1) {
+            const double z = y * y;
+            const double w = z * y;
+            const double p1 = t0 + w * (t3 + w * (t6 + w * (t9 + w * t12)));
+            const double p2 = t1 + w * (t4 + w * (t7 + w * (t10 + w * t13)));
+            const double p3 = t2 + w * (t5 + w * (t8 + w * (t11 + w * t14)));
+            const double p = z * p1 - (tt - w * (p2 + y * p3));
+            r += (tf + p);
+        } else {
+            const double p1 = y * (u0 + y * (u1 + y * (u2 + y * (u3 + y * (u4 + y * u5)))));
+            const double p2 = 1.0 + y * (v1 + y * (v2 + y * (v3 + y * (v4 + y * v5))));
+            r += (-0.5 * y + p1 / p2);
+        }
+    } else if (ix < 0x40200000u) {                          // 2 <= x < 8
+        const int i = (int)x;
+        const double y = x - (double)i;
+        const double p = y * (s0 + y * (s1 + y * (s2 + y * (s3 + y * (s4 + y * (s5 + y * s6))))));
+        const double q = 1.0 + y * (r1 + y * (r2 + y * (r3 + y * (r4 + y * (r5 + y * r6)))));
+        r = 0.5 * y + p / q;
+        double z = 1.0;                                     // lgamma(1 + s) = log(s) + lgamma(s)
+        if (i >= 7) z *= (y + 6.0);
+        if (i >= 6) z *= (y + 5.0);
+        if (i >= 5) z *= (y + 4.0);
+        if (i >= 4) z *= (y + 3.0);
+        if (i >= 3) { z *= (y + 2.0); r += mp_log(z); }
+    } else if (ix < 0x43900000u) {                          // 8 <= x < 2^58
+        const double t = mp_log(x);
+        const double z = 1.0 / x;
+        const double y = z * z;
+        const double w = w0 + z * (w1 + y * (w2 + y * (w3 + y * (w4 + y * (w5 + y * w6)))));
+        r = (x - 0.5) * (t - 1.0) + w;
+    } else {
+        r = x * (mp_log(x) - 1.0);
+    }
+    return r;
+}

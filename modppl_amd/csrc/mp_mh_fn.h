@@ -500,3 +500,4 @@ static int mp_mh_register_proposal(int kind, bool (*parse)(const double*, int, P
 #define MP_REGISTER_MH_MODEL(KIND, TYPE, PARSE) static const int mp_mh_registered_##TYPE = mp_mh_register_model<TYPE>(KIND, PARSE);
 #define MP_REGISTER_MH_PROPOSAL(KIND, MODEL, TYPE, PARSE) static const int mp_mh_registered_##TYPE = mp_mh_register_proposal<MODEL, TYPE>(KIND, PARSE);
 #include "mp_mh_models.h"
+#include "mp_mh_models_counts.h"

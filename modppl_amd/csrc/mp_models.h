@@ -130,6 +130,15 @@ struct mp_generate_handler {
             return mp_uniform_sample(st, a, b);
         }
     }
+    // an observed count (mp_dists.h); a latent count has no place in a filter model: the normals are the only pre-drawn choices
+    template <int SITE>
+    MP_HD double poisson(double rate) {
+        constexpr int k = Model::obs_of(SITE);
+        static_assert(k >= 0, "poisson: the site must be observed on this path");
+        const double x = obs[k];
+        weight += mp_poisson_logpdf(x, rate);
+        return x;
+    }
 };
 
 // ---------------------------------------------------------------------------------------
@@ -199,6 +208,14 @@ struct mp_simulate_handler {
     MP_HD double uniform(double a, double b) {
         mp_site st(rng, MP_DOM_MODEL, (uint32_t)SITE);
         return mp_uniform_sample(st, a, b);
+    }
+    template <int SITE>
+    MP_HD double poisson(double rate) {
+        mp_site st(rng, MP_DOM_MODEL, (uint32_t)SITE);
+        const double x = mp_poisson_sample(st, rate);
+        constexpr int k = Model::obs_of(SITE);
+        if constexpr (k >= 0) obs_out[k] = x;
+        return x;
     }
 };
 

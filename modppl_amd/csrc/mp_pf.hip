@@ -48,6 +48,7 @@ template <class M>
 int mp_register_model_hip(int kind, bool (*parse)(const mp_model_desc&, M&, std::string&));
 #define MP_MODEL_REGISTRAR mp_register_model_hip
 #include "mp_models.h"
+#include "mp_models_counts.h"   // (models whose sites the CPU checker's handlers do not know)
 
 typedef unsigned long long u64;
 

@@ -43,6 +43,39 @@ __global__ void k_probe_u01(uint32_t k0, uint32_t k1, uint32_t slot0, uint32_t s
     out[2 * i + 1] = mp_u01(b.b);
 }
 
+// the count and positive-real distributions of mp_dists.h (dist / op: include/modppl_hip_probe.h mp_probe_dist)
+__global__ void k_probe_dist(int dist, int op, const double* x, const double* p0, const double* p1, long long n, uint32_t k0, uint32_t k1,
+                             uint32_t slot0, uint32_t step, uint32_t domain, uint32_t site, double* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double a = p0 ? p0[i] : 0., b = p1 ? p1[i] : 0.;
+    double r = 0.;
+    if (op == 0) {
+        const double v = x[i];
+        switch (dist) {
+        case MP_PROBE_DIST_POISSON: r = mp_poisson_logpdf(v, a); break;
+        case MP_PROBE_DIST_GAMMA: r = mp_gamma_logpdf(v, a, b); break;
+        case MP_PROBE_DIST_BETA: r = mp_beta_logpdf(v, a, b); break;
+        case MP_PROBE_DIST_GEOMETRIC: r = mp_geometric_logpdf(v, a); break;
+        case MP_PROBE_DIST_UNIFORM_DISCRETE: r = mp_uniform_discrete_logpdf(v, a, b); break;
+        case MP_PROBE_DIST_LGAMMA: r = mp_lgamma(v); break;
+        case MP_PROBE_DIST_LOG1P: r = mp_log1p(v); break;
+        }
+    } else {
+        mp_stream s;
+        s.k0 = k0; s.k1 = k1; s.slot = slot0 + (uint32_t)i; s.step = step;
+        mp_site st(s, domain, site);
+        switch (dist) {
+        case MP_PROBE_DIST_POISSON: r = mp_poisson_sample(st, a); break;
+        case MP_PROBE_DIST_GAMMA: r = mp_gamma_sample(st, a, b); break;
+        case MP_PROBE_DIST_BETA: r = mp_beta_sample(st, a, b); break;
+        case MP_PROBE_DIST_GEOMETRIC: r = mp_geometric_sample(st, a); break;
+        case MP_PROBE_DIST_UNIFORM_DISCRETE: r = mp_uniform_discrete_sample(st, a, b); break;
+        }
+    }
+    out[i] = r;
+}
+
 // mvnormal (mvnormal.rs:14-38) of dimension k <= MP_PROBE_MAX_K with the covariance constants hoisted by the host (mp_linalg.h;
 // the reference takes any k; model sites are compiled for k <= 16, this general-k form serves the distribution on its own):
 #define MP_PROBE_MAX_K 64
@@ -178,6 +211,28 @@ int32_t mp_probe_mvnormal(int32_t k, int32_t chain, const double* x, const doubl
     }
 done:
     (void)hipFree(dx); (void)hipFree(dmu); (void)hipFree(dm); (void)hipFree(dout);
+    return rc;
+}
+
+int32_t mp_probe_dist(int32_t dist, int32_t op, const double* x, const double* p0, const double* p1, int64_t n, uint64_t seed, uint32_t slot0,
+                      uint32_t step, uint32_t domain, uint32_t site, double* out, int32_t device) {
+    if (dist < 0 || dist > MP_PROBE_DIST_LOG1P || (op != 0 && op != 1) || (op == 0 && !x) || (op == 1 && dist > MP_PROBE_DIST_UNIFORM_DISCRETE) ||
+        n < 1 || !out)
+        return MP_ERR_INVALID_ARG;
+    int32_t rc = MP_OK;
+    double *dx = nullptr, *dp0 = nullptr, *dp1 = nullptr, *dout = nullptr;
+    const size_t bytes = sizeof(double) * (size_t)n;
+    PCK(hipSetDevice(device));
+    PCK(hipMalloc(&dout, bytes));
+    if (op == 0) { PCK(hipMalloc(&dx, bytes)); PCK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice)); }
+    if (p0) { PCK(hipMalloc(&dp0, bytes)); PCK(hipMemcpy(dp0, p0, bytes, hipMemcpyHostToDevice)); }
+    if (p1) { PCK(hipMalloc(&dp1, bytes)); PCK(hipMemcpy(dp1, p1, bytes, hipMemcpyHostToDevice)); }
+    hipLaunchKernelGGL(k_probe_dist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)dist, (int)op, dx, dp0, dp1, (long long)n,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), slot0, step, domain, site, dout);
+    PCK(hipGetLastError());
+    PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+done:
+    (void)hipFree(dx); (void)hipFree(dp0); (void)hipFree(dp1); (void)hipFree(dout);
     return rc;
 }
 

@@ -88,3 +88,18 @@ def stochastic_volatility_model(mu=-1.0, phi=0.95, sigma=0.25, sig0=0.8):
     """Stochastic volatility: h_0 ~ normal(mu, sig0); h_t ~ normal(mu + phi (h_{t-1} - mu), sigma); y_t ~ normal(0, exp(h_t / 2))
     observed.  The example model of the registration layer: its whole definition is one block of mp_models_extra.h."""
     return UnfoldModel(MP_MODEL_STOCHVOL, 1, 1, [mu, phi, sigma, sig0], "stochvol")
+
+
+MP_MODEL_POISSON_SSM = 101   # registered through MP_REGISTER_UNFOLD_MODEL (modppl_amd/csrc/mp_models_counts.h)
+
+# generative functions over the count and positive-real distributions (modppl_amd/csrc/mp_mh_models_counts.h), for FunctionChains /
+# fn_importance_sampling; observations are constraints on their sites, counts as floats
+MP_FN_POISSON_UPDATE = 130    # k ~ poisson(rate) at site 0; value_i ~ uniform(0, 1) at site 1 + i, i < k <= 31.  params [] or [rate]
+MP_FN_CHANGEPOINT = 131       # tau ~ uniform_discrete(1, n-1) (site 0); l1, l2 ~ gamma(a, scale b) (1, 2); y_j ~ poisson (3 + j).  params [n, a, b]
+MP_FN_BETA_GEOMETRIC = 132    # p ~ beta(a, b) (site 0); k_j ~ geometric(p) (1 + j).  params [n, a, b]
+
+
+def poisson_state_space_model(mu=0.5, phi=0.9, sigma=0.3, sig0=0.5):
+    """Poisson state-space model: h_0 ~ normal(mu, sig0); h_t ~ normal(mu + phi (h_{t-1} - mu), sigma); y_t ~ poisson(exp(h_t))
+    observed (the counts as floats; a negative or non-integer count has probability 0)."""
+    return UnfoldModel(MP_MODEL_POISSON_SSM, 1, 1, [mu, phi, sigma, sig0], "poisson_ssm")

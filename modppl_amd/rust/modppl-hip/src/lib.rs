@@ -464,3 +464,4 @@ macro_rules! unfold_model {
     };
 }
 unfold_model!(stochastic_volatility, kind = 100, dim_state = 1, dim_obs = 1, params = [mu, phi, sigma, sig0]);
+unfold_model!(poisson_state_space, kind = 101, dim_state = 1, dim_obs = 1, params = [mu, phi, sigma, sig0]);

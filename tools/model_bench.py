@@ -2,7 +2,7 @@
 """Per-model step times on one MI355X (BASELINE.json configs C2, C3, C5-per-GPU shard, C4): not the contract bench
 (bench.py is), just the numbers DESIGN.md quotes for the other configurations.
 
-    python tools/model_bench.py [--steps 30] [--which c2,c3,c5,c4]
+    python tools/model_bench.py [--steps 30] [--which c2,c3,c5,c4,counts]
 """
 import argparse
 import json
@@ -110,6 +110,25 @@ def main():
         ch.mh(0.1, n_iters=60)
         dt = time.perf_counter() - t0
         out.append({"case": "C4 drift-proposal MH sigma=0.1", "chains": 1 << 20, "chain_iterations_per_s": (1 << 20) * 60 / dt})
+    if "counts" in which:   # the Poisson state-space model (unfold 101) against stochastic volatility (100): the same two-tile k_propagate_mt
+        h, ys_sv, ys_po = -1.0, [], []
+        for t in range(T):
+            h = -1.0 + 0.95 * (h + 1.0) + rng.normal(0, 0.25)
+            ys_sv.append(rng.normal(0, np.exp(h / 2)))
+            ys_po.append(float(rng.poisson(np.exp(0.5 + h))))
+        out.append(pf_case("stochastic volatility (kind 100), 2^20", modppl_amd.stochastic_volatility_model(), 1 << 20, np.array(ys_sv).reshape(T, 1),
+                           args.steps, args.warmup, 96, args.sharded, args.scheme))
+        out.append(pf_case("Poisson state-space (kind 101), 2^20", modppl_amd.poisson_state_space_model(), 1 << 20, np.array(ys_po).reshape(T, 1),
+                           args.steps, args.warmup, 96, args.sharded, args.scheme))
+        from modppl_amd.models import MP_FN_CHANGEPOINT
+        y = np.concatenate([rng.poisson(2.0, 10), rng.poisson(7.0, 10)]).astype(np.float64)
+        fc = modppl_amd.FunctionChains(MP_FN_CHANGEPOINT, [y.size, 2.0, 2.0], {3 + j: v for j, v in enumerate(y)}, 1 << 20, 20241008)
+        fc.regen_mh([0, 1, 2], n_iters=30, cycle=True)   # (returns when the launch has finished: it reads the acceptance count)
+        t0 = time.perf_counter()
+        fc.regen_mh([0, 1, 2], n_iters=300, cycle=True)
+        dt = time.perf_counter() - t0
+        out.append({"case": "regen-MH Poisson change point (kind 131, n = 20), masks cycle tau,l1,l2", "chains": 1 << 20,
+                    "chain_iterations_per_s": (1 << 20) * 300 / dt})
     for o in out:
         print(json.dumps(o))
 
