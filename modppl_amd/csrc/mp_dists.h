@@ -251,12 +251,24 @@ MP_HD double mp_gamma_mt(mp_site& st, double d) {
     return d;
 }
 // Gamma(a, 1): a >= 1 directly; a < 1 as Gamma(a + 1) U^(1/a), formed in log space (ln G + ln U / a, U = 1 - u01 in (0, 1]: the next
-// block after the ones of Gamma(a + 1)) so that U^(1/a) does not underflow on its own
-MP_HD double mp_gamma_std_sample(mp_site& st, double a) {
-    if (a >= 1.) return mp_gamma_mt(st, a - 1. / 3.);
+// block after the ones of Gamma(a + 1)) so that U^(1/a) does not underflow on its own.  mp_gamma_std_log_sample puts the variate in *x
+// and returns its logarithm, which stays finite where the variate itself underflows to 0; mp_gamma_std_sample is its variate.
+MP_HD double mp_gamma_std_log_sample(mp_site& st, double a, double* x) {
+    if (a >= 1.) {
+        *x = mp_gamma_mt(st, a - 1. / 3.);
+        return mp_log(*x);
+    }
     const double g = mp_gamma_mt(st, (a + 1.) - 1. / 3.);
     const double lu = mp_log(1. - mp_u01(st.next_block().a));
-    return mp_exp(mp_log(g) + lu / a);
+    const double l = mp_log(g) + lu / a;
+    *x = mp_exp(l);
+    return l;
+}
+MP_HD double mp_gamma_std_sample(mp_site& st, double a) {
+    if (a >= 1.) return mp_gamma_mt(st, a - 1. / 3.);
+    double x;
+    mp_gamma_std_log_sample(st, a, &x);
+    return x;
 }
 MP_HD double mp_gamma_sample(mp_site& st, double a, double b) {
     if (!(a > 0.) || !(b > 0.) || a == MP_INF || b == MP_INF) return MP_NAN;
@@ -270,12 +282,15 @@ MP_HD double mp_beta_logpdf(double x, double a, double b) {
     if (!(x > 0. && x < 1.)) return MP_NEG_INF;
     return mp_lgamma(a + b) - mp_lgamma(a) - mp_lgamma(b) + (a - 1.) * mp_log(x) + (b - 1.) * mp_log1p(-x);
 }
-// X / (X + Y), X ~ Gamma(a, 1) then Y ~ Gamma(b, 1) from the same stream
+// X / (X + Y), X ~ Gamma(a, 1) then Y ~ Gamma(b, 1) from the same stream.  Where that quotient cannot be formed (for small shapes
+// both gammas can underflow to 0, and 0 / 0 would fail both clamps), the same pair in log form: 1 / (1 + exp(ln Y - ln X)).
 MP_HD double mp_beta_sample(mp_site& st, double a, double b) {
     if (!(a > 0.) || !(b > 0.) || a == MP_INF || b == MP_INF) return MP_NAN;
-    const double X = mp_gamma_std_sample(st, a);
-    const double Y = mp_gamma_std_sample(st, b);
-    const double x = X / (X + Y);
+    double X, Y;
+    const double lX = mp_gamma_std_log_sample(st, a, &X);
+    const double lY = mp_gamma_std_log_sample(st, b, &Y);
+    const double s = X + Y;
+    const double x = (X > 0. && Y > 0. && s < MP_INF) ? X / s : 1. / (1. + mp_exp(lY - lX));
     return x < MP_MIN_NORMAL ? MP_MIN_NORMAL : (x < 1. ? x : MP_ONE_MINUS_ULP);
 }
 

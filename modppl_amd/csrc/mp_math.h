@@ -187,6 +187,8 @@ MP_HD int mp_rem_pio2(double x, double* y0, double* y1) {
     const double P1T = 6.07710050650619224932e-11;  // pi/2 - P1
     const double P2 = 6.07710050630396597660e-11;   // second 33 bits
     const double P2T = 2.02226624879595063154e-21;  // pi/2 - (P1 + P2)
+    const double P3 = 2.02226624871116645580e-21;   // third 33 bits
+    const double P3T = 8.47842766036889956997e-32;  // pi/2 - (P1 + P2 + P3)
     if (!(fabs(x) < 1647099.0)) return -1;           // also catches NaN / inf
     const double fn = rint(x * INVPIO2);
     double r = x - fn * P1;                          // exact: fn < 2^21, P1 has 33 bits
@@ -196,11 +198,20 @@ MP_HD int mp_rem_pio2(double x, double* y0, double* y1) {
     const int ex = (int)((mp_f2u(x) >> 52) & 0x7FF);
     const int ey = (int)((mp_f2u(y) >> 52) & 0x7FF);
     if (ex - ey > 16) {
-        const double t = r;
+        double t = r;
         w = fn * P2;
         r = t - w;
         w = fn * P2T - ((t - r) - w);
         y = r - w;
+        // third when even that left fewer than 4 significant bits of the tail (difference > 49): x within ~2^-50 |x| of a multiple
+        // of pi/2 (413441.44719405076, n = 263205, cancels 70 bits; two iterations err by 1.06 ulp there)
+        if (ex - (int)((mp_f2u(y) >> 52) & 0x7FF) > 49) {
+            t = r;
+            w = fn * P3;
+            r = t - w;
+            w = fn * P3T - ((t - r) - w);
+            y = r - w;
+        }
     }
     *y0 = y;
     *y1 = (r - y) - w;
@@ -284,9 +295,12 @@ MP_HD double mp_atan2(double y, double x) {
     }
     if (ay == MP_INF) return yneg ? -PI / 2 : PI / 2;
     const int ex = (int)((ux >> 52) & 0x7FF), ey = (int)((uy >> 52) & 0x7FF);
+    if (ey - ex > 60) {                                   // |y/x| > 2^60: +-pi/2 whatever the sign of x (e_atan2.c's m &= 1)
+        const double r = PI / 2 + 0.5 * PI_LO;
+        return yneg ? -r : r;
+    }
     double z;
-    if (ey - ex > 60) z = PI / 2 + 0.5 * PI_LO;           // |y/x| > 2^60
-    else if (xneg && (ex - ey) > 60) z = 0.0;             // |y/x| < 2^-60, x < 0
+    if (xneg && (ex - ey) > 60) z = 0.0;                  // |y/x| < 2^-60, x < 0
     else z = mp_atan(fabs(y / x));
     if (!xneg) return yneg ? -z : z;
     const double r = PI - (z - PI_LO);

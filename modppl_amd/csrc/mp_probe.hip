@@ -22,6 +22,9 @@ __global__ void k_probe_math(int op, const double* a, const double* b, const dou
     case MP_PROBE_NORMAL_LOGPDF: r = mp_normal_logpdf(a[i], b[i], c[i]); break;
     case MP_PROBE_NORMAL_LOGPDF_H: r = mp_normal_logpdf_h(a[i], b[i], c[i], mp_log(c[i]), mp_rcp_hoist(c[i])); break;
     case MP_PROBE_DIV_HOISTED: r = mp_rcp_hoistable(b[i]) ? mp_div_hoisted(a[i], b[i], 1.0 / b[i]) : a[i] / b[i]; break;
+    case MP_PROBE_SIN: r = mp_sin(a[i]); break;
+    case MP_PROBE_COS: r = mp_cos(a[i]); break;
+    case MP_PROBE_ATAN2: r = mp_atan2(a[i], b[i]); break;
     }
     out[i] = r;
 }
@@ -133,6 +136,7 @@ __global__ void k_probe_mfma_f64(const double* A, const double* B, const double*
 extern "C" {
 
 int32_t mp_probe_math(int32_t op, const double* a, const double* b, const double* c, int64_t n, double* out, int32_t device) {
+    if (op < MP_PROBE_EXP || op > MP_PROBE_ATAN2 || !a || !out || n < 1) return MP_ERR_INVALID_ARG;
     int32_t rc = MP_OK;
     double *da = nullptr, *db = nullptr, *dc = nullptr, *dout = nullptr;
     const size_t bytes = sizeof(double) * (size_t)n;

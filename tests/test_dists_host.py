@@ -229,3 +229,39 @@ def test_draws_are_a_function_of_the_site_stream():
     assert np.array_equal(a, S.sample(S.GAMMA, 1000, 0.7, 2., seed=9, step=3, site=4))
     assert not np.array_equal(a, S.sample(S.GAMMA, 1000, 0.7, 2., seed=9, step=3, site=5))
     assert np.array_equal(a[10:], S.sample(S.GAMMA, 990, 0.7, 2., seed=9, step=3, site=4, slot0=10))
+
+
+# ---- small shapes: both gammas of a beta can underflow to 0 (Gamma(a) for a < 1 is Gamma(a + 1) U^(1/a)); the beta is then formed
+# from their logarithms instead of as 0 / 0 ----
+
+@pytest.mark.parametrize("a", [1e-3, 2e-3, 5e-3, 0.02])
+def test_beta_small_symmetric_shapes_are_symmetric(a):
+    """Beta(a, a) puts mass 1/2 on each side of 1/2; 10^6 draws, 5 sigma"""
+    x = S.sample(S.BETA, N, a, a, seed=606)
+    assert np.isfinite(x).all() and x.min() >= 2. ** -1022 and x.max() <= 1. - 2. ** -53
+    p = (x > 0.5).mean()
+    assert abs(p - 0.5) <= 5 * math.sqrt(0.25 / N), (a, p)
+
+
+@pytest.mark.parametrize("ab,points", [((1e-3, 5.), [1e-300, 1e-200, 1e-100, 1e-30, 1e-10, 1e-3, 0.1, 0.5]),
+                                       ((5., 1e-3), [0.3, 0.6, 0.9, 0.99, 1. - 1e-6, 1. - 1e-12, 1. - 2. ** -50])])
+def test_beta_small_shape_cdf(ab, points):
+    """the empirical cdf at a handful of points against the regularised incomplete beta (mpmath.betainc)"""
+    a, b = ab
+    x = S.sample(S.BETA, N, a, b, seed=707)
+    for t in points:
+        F = float(mpmath.betainc(a, b, 0, t, regularized=True))
+        e = (x <= t).mean()
+        assert abs(e - F) <= 5 * math.sqrt(F * (1. - F) / N) + 1e-12, (ab, t, e, F)
+
+
+def test_gamma_tiny_shape_clamped_share():
+    """Gamma(10^-3, 1): the variates that underflow are clamped to 2^-1022; their share is P(X <= 2^-1022), the regularised lower
+    incomplete gamma there"""
+    a = 1e-3
+    x = S.sample(S.GAMMA, N, a, 1., seed=808)
+    t = 2. ** -1022
+    assert x.min() >= t
+    F = float(mpmath.gammainc(a, 0, mpmath.mpf(t), regularized=True))
+    share = (x == t).mean()
+    assert abs(share - F) <= 5 * math.sqrt(F * (1. - F) / N), (share, F)

@@ -78,3 +78,17 @@ def test_sample_bits_device_equal_host(dist):
     host = S.sample(dist, N, a, b, seed=seed, slot0=slot0, step=step, domain=domain, site=site)
     assert same_bits(dev, host)
     assert np.isfinite(dev).all()
+
+
+def test_small_shape_beta_and_gamma_sample_bits_device_equal_host():
+    """shapes down to 10^-3, where both gammas of a beta underflow and the sampler takes its log form: device == host, bit for bit"""
+    rng = np.random.default_rng(300)
+    a = np.exp(rng.uniform(np.log(1e-3), np.log(0.1), N))
+    b = np.where(rng.uniform(size=N) < 0.5, a, np.exp(rng.uniform(np.log(1e-3), np.log(20.), N)))
+    dev = probe(S.BETA, 1, None, a, b, N, 99, 0, 2, 0, 7)
+    host = S.sample(S.BETA, N, a, b, seed=99, step=2, site=7)
+    assert same_bits(dev, host)
+    assert np.isfinite(dev).all() and dev.min() >= 2. ** -1022 and dev.max() <= 1. - 2. ** -53
+    assert (dev == 2. ** -1022).any() and (dev == 1. - 2. ** -53).any()   # the clamps are reached on both sides
+    dev = probe(S.GAMMA, 1, None, a, 1., N, 99, 0, 3, 0, 7)
+    assert same_bits(dev, S.sample(S.GAMMA, N, a, 1., seed=99, step=3, site=7))

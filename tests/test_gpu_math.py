@@ -104,3 +104,38 @@ def test_philox_stream_and_sampler(hiplib, oracle):
         assert s[i] == oracle.oracle_normal_random(123, i, 9, 0, 0, 1.64, 0.025, 1)
     # modppl/tests/dists.rs:113-118 moment check
     assert abs(s.mean() - 1.64) < 0.001 and abs(s.std(ddof=1) - 0.025) < 0.001
+
+
+def test_sin_cos_atan2_bitwise(hiplib, oracle):
+    """mp_sin / mp_cos / mp_atan2 on the device == the host's bits over the sets tests/test_trig_exact.py checks against exact
+    references: random arguments over the whole domain, the doubles next to n pi/2, the domain's edges, and atan2's quadrants,
+    exponent ratios and special cases"""
+    from tests import test_trig_exact as T
+
+    rng = np.random.default_rng(9)
+    n = 1 << 19
+    x = np.concatenate([rng.uniform(-10, 10, n), rng.uniform(-T.DOMAIN, T.DOMAIN, n), T.near_multiples_of_pio2(),
+                        np.ldexp(rng.uniform(1, 2, n), rng.integers(-1074, 0, n)),
+                        [0.0, -0.0, 5e-324, T.DOMAIN, -T.DOMAIN, np.nextafter(T.DOMAIN, 0), np.inf, -np.inf, np.nan]])
+    for op, f in ((7, T._sin), (8, T._cos)):
+        got, want = _probe(hiplib, op, x), f(oracle, x)
+        nan = np.isnan(want)
+        assert np.array_equal(np.isnan(got), nan)
+        assert np.array_equal(_bits(got[~nan]), _bits(want[~nan])), op
+    y, xx = T._random_pairs(rng, 1 << 20)
+    sv = np.array([0.0, -0.0, 1.0, -1.0, np.inf, -np.inf, np.nan, 5e-324, 2.0 ** 61, -(2.0 ** -61)])
+    gy, gx = np.meshgrid(sv, sv)
+    y, xx = np.concatenate([y, rng.normal(0, 1, n), gy.ravel()]), np.concatenate([xx, rng.normal(0, 1, n), gx.ravel()])
+    got, want = _probe(hiplib, 9, y, xx), T._atan2(oracle, y, xx)
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan)
+    assert np.array_equal(_bits(got[~nan]), _bits(want[~nan]))
+
+
+def test_probe_math_rejects_an_unknown_op(hiplib):
+    from modppl_amd import capi
+
+    a = np.zeros(4)
+    out = np.empty(4)
+    assert hiplib.mp_probe_math(10, a.ctypes.data_as(DP), None, None, 4, out.ctypes.data_as(DP), 0) == capi.MP_ERR_INVALID_ARG
+    assert hiplib.mp_probe_math(-1, a.ctypes.data_as(DP), None, None, 4, out.ctypes.data_as(DP), 0) == capi.MP_ERR_INVALID_ARG
