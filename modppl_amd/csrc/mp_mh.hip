@@ -23,6 +23,7 @@
 
 #include "../../include/modppl_hip.h"
 #include "mp_dists.h"
+#include "mp_hip_own.h"
 #include "mp_linalg.h"
 
 typedef unsigned long long u64;
@@ -382,30 +383,29 @@ __global__ __launch_bounds__(MH_THREADS) void k_pointed_logjp(u64 n, pointed_par
 }
 
 struct mh_fn_ops;   // mp_mh_fn.h: chains of a registered generative function
-struct mp_mh {
+struct mp_mh {           // (every device pointer is a holder, mp_hip_own.h; the stream is declared first so that it outlives them)
+    mp_hip_stream stream;
     u64 n = 0, seed = 0;
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     mh_data data{};
     double ln_noise = 0.;
-    int* is_lin = nullptr;
-    double *a = nullptr, *b = nullptr, *c = nullptr, *tmp = nullptr;
-    u64* d_acc = nullptr;
+    mp_dev<int> is_lin;
+    mp_dev<double> a, b, c, tmp;
+    mp_dev<u64> d_acc;
     u64 iters = 0;
     int kind = MP_MH_MODEL_HIERARCHICAL;
     pointed_params pointed{};
-    double* lat = nullptr;   // pointed model: [n][2]
-    double* ys_chain = nullptr;   // [n][n_data]: per-chain "(y, i)" choices once an empty-mask regenerate re-simulated them
+    mp_dev<double> lat;        // pointed model: [n][2]
+    mp_dev<double> ys_chain;   // [n][n_data]: per-chain "(y, i)" choices once an empty-mask regenerate re-simulated them
     std::shared_ptr<mh_fn_ops> fn;   // registered function: the trace table below replaces the fields above
-    double* fvals = nullptr;         // [2 n_sites][n]: values, then the sub-tries' running weights
-    uint32_t* fpresent = nullptr;    // [n]
+    mp_dev<double> fvals;            // [2 n_sites][n]: values, then the sub-tries' running weights
+    mp_dev<uint32_t> fpresent;       // [n]
     // scratch of the standalone GFI calls (mp_fn_*), allocated on first use
-    double* gfi_vals = nullptr;      // [n_sites][n]: the discard of an update / the choices of a proposal
-    uint32_t* gfi_present = nullptr; // [n]
-    double* gfi_cons = nullptr;      // [n_sites][n]: per-chain constraint values
-    uint32_t* gfi_cpresent = nullptr; // [n]: per-chain constraint presence
-    double* d_data = nullptr;        // models with declared data sites (mp_genfn.h): [2][n_obs] = the covariates (params), the observed values
+    mp_dev<double> gfi_vals;         // [n_sites][n]: the discard of an update / the choices of a proposal
+    mp_dev<uint32_t> gfi_present;    // [n]
+    mp_dev<double> gfi_cons;         // [n_sites][n]: per-chain constraint values
+    mp_dev<uint32_t> gfi_cpresent;   // [n]: per-chain constraint presence
+    mp_dev<double> d_data;           // models with declared data sites (mp_genfn.h): [2][n_obs] = the covariates (params), the observed values
 };
 #include "mp_mh_fn.h"
 
@@ -445,14 +445,14 @@ int32_t mp_mh_create(int32_t model_kind, const double* xs, const double* ys, int
     for (int k = 0; k < MH_MAX_DATA; ++k) { h->data.xs[k] = k < n_data ? xs[k] : 0.; h->data.ys[k] = k < n_data ? ys[k] : 0.; }
     h->ln_noise = mp_log(MH_NOISE);
     MHCK(hipSetDevice(device));
-    if (stream) h->stream = (hipStream_t)stream;
-    else { MHCK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-    MHCK(hipMalloc(&h->is_lin, sizeof(int) * n_chains));
-    MHCK(hipMalloc(&h->a, sizeof(double) * n_chains));
-    MHCK(hipMalloc(&h->b, sizeof(double) * n_chains));
-    MHCK(hipMalloc(&h->c, sizeof(double) * n_chains));
-    MHCK(hipMalloc(&h->tmp, sizeof(double) * n_chains * 4));
-    MHCK(hipMalloc(&h->d_acc, sizeof(u64)));
+    if (stream) h->stream.borrow((hipStream_t)stream);
+    else MHCK(h->stream.create(hipStreamNonBlocking));
+    MHCK(mp_hipMalloc(h->is_lin, n_chains));
+    MHCK(mp_hipMalloc(h->a, n_chains));
+    MHCK(mp_hipMalloc(h->b, n_chains));
+    MHCK(mp_hipMalloc(h->c, n_chains));
+    MHCK(mp_hipMalloc(h->tmp, n_chains * 4));
+    MHCK(mp_hipMalloc(h->d_acc, 1));
     hipLaunchKernelGGL(k_mh_init, dim3((unsigned)((n_chains + MH_THREADS - 1) / MH_THREADS)), dim3(MH_THREADS), 0, h->stream, h->n,
                        (uint32_t)seed, (uint32_t)(seed >> 32), constrain_is_linear, h->is_lin, h->a, h->b, h->c);
     MHCK(hipGetLastError());
@@ -513,11 +513,11 @@ int32_t mp_mh_create_pointed(const double* bounds, const double* obs_cov, const 
     P.ln_det_cov = mp_log(det);
     P.obs[0] = obs[0]; P.obs[1] = obs[1];
     MHCK(hipSetDevice(device));
-    if (stream) h->stream = (hipStream_t)stream;
-    else { MHCK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-    MHCK(hipMalloc(&h->lat, sizeof(double) * 2 * n_chains));
-    MHCK(hipMalloc(&h->tmp, sizeof(double) * n_chains));
-    MHCK(hipMalloc(&h->d_acc, sizeof(u64)));
+    if (stream) h->stream.borrow((hipStream_t)stream);
+    else MHCK(h->stream.create(hipStreamNonBlocking));
+    MHCK(mp_hipMalloc(h->lat, 2 * n_chains));
+    MHCK(mp_hipMalloc(h->tmp, n_chains));
+    MHCK(mp_hipMalloc(h->d_acc, 1));
     hipLaunchKernelGGL(k_pointed_init, dim3((unsigned)((n_chains + MH_THREADS - 1) / MH_THREADS)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)seed,
                        (uint32_t)(seed >> 32), P, h->lat);
     MHCK(hipGetLastError());
@@ -546,12 +546,12 @@ static int32_t fn_alloc(int32_t model_kind, const double* params, int32_t n_para
     h->fn = ops;
     h->n = n_chains; h->seed = seed; h->device = device;
     MHCK(hipSetDevice(device));
-    if (stream) h->stream = (hipStream_t)stream;
-    else { MHCK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-    MHCK(hipMalloc(&h->fvals, sizeof(double) * n_chains * 2 * (size_t)ops->ns()));   // [n_sites] values + [n_sites] sub-trie running weights (rows of sub-call ids)
-    MHCK(hipMalloc(&h->fpresent, sizeof(uint32_t) * n_chains * (size_t)fn_words(ops->ns())));
-    MHCK(hipMalloc(&h->tmp, sizeof(double) * n_chains));
-    MHCK(hipMalloc(&h->d_acc, sizeof(u64) * 2));
+    if (stream) h->stream.borrow((hipStream_t)stream);
+    else MHCK(h->stream.create(hipStreamNonBlocking));
+    MHCK(mp_hipMalloc(h->fvals, n_chains * 2 * (size_t)ops->ns()));   // [n_sites] values + [n_sites] sub-trie running weights (rows of sub-call ids)
+    MHCK(mp_hipMalloc(h->fpresent, n_chains * (size_t)fn_words(ops->ns())));
+    MHCK(mp_hipMalloc(h->tmp, n_chains));
+    MHCK(mp_hipMalloc(h->d_acc, 2));
     MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
     MHCK(hipMemsetAsync(h->fpresent, 0, sizeof(uint32_t) * n_chains * (size_t)fn_words(ops->ns()), h->stream));
     out = std::move(h);
@@ -595,7 +595,7 @@ static int32_t fn_create_generate(int32_t model_kind, const double* params, int3
             if (!seen[(size_t)j])
                 return mp_set_error(MP_ERR_UNSUPPORTED, "every declared data site must be constrained (an observation drawn from its prior would be per-chain state: "
                                                         "write the model with ordinary sites for that)");
-        MHCK(hipMalloc(&h->d_data, sizeof(double) * buf.size()));
+        MHCK(mp_hipMalloc(h->d_data, buf.size()));
         MHCK(hipMemcpyAsync(h->d_data, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
         MHCK(hipStreamSynchronize(h->stream));   // (`buf` is a local)
         h->fn->bind_data(h->d_data, h->d_data + nd);
@@ -804,7 +804,7 @@ int32_t mp_regen_mh_step(mp_mh* h, const int32_t* mask_sites, int32_t n_mask, in
         MHCK(hipSetDevice(h->device));
         const unsigned grid = (unsigned)((h->n + MH_THREADS - 1) / MH_THREADS);
         if (!h->ys_chain) {
-            MHCK(hipMalloc(&h->ys_chain, sizeof(double) * h->n * (size_t)h->data.n));
+            MHCK(mp_hipMalloc(h->ys_chain, h->n * (size_t)h->data.n));
             hipLaunchKernelGGL(k_mh_broadcast_ys, dim3(grid), dim3(MH_THREADS), 0, h->stream, h->n, h->data, h->ys_chain);
         }
         MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64), h->stream));
@@ -891,11 +891,14 @@ struct gfi_cons {
 };
 static int32_t gfi_scratch(mp_mh* h) {
     const size_t ns = (size_t)h->fn->ns();
-    if (!h->gfi_vals) {
-        MHCK(hipMalloc(&h->gfi_vals, sizeof(double) * ns * h->n));
-        MHCK(hipMalloc(&h->gfi_present, sizeof(uint32_t) * h->n * (size_t)fn_words_of(h)));
-        MHCK(hipMalloc(&h->gfi_cons, sizeof(double) * ns * h->n));
-        MHCK(hipMalloc(&h->gfi_cpresent, sizeof(uint32_t) * h->n * (size_t)fn_words_of(h)));
+    if (!h->gfi_vals) {   // all four or none: the handle gets them only when every allocation succeeded
+        mp_dev<double> vals, cons;
+        mp_dev<uint32_t> present, cpresent;
+        MHCK(mp_hipMalloc(vals, ns * h->n));
+        MHCK(mp_hipMalloc(present, h->n * (size_t)fn_words_of(h)));
+        MHCK(mp_hipMalloc(cons, ns * h->n));
+        MHCK(mp_hipMalloc(cpresent, h->n * (size_t)fn_words_of(h)));
+        h->gfi_vals = std::move(vals); h->gfi_present = std::move(present); h->gfi_cons = std::move(cons); h->gfi_cpresent = std::move(cpresent);
     }
     return MP_OK;
 }
@@ -1068,10 +1071,6 @@ int32_t mp_mh_destroy(mp_mh* h) {
     if (!h) return MP_OK;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->is_lin); (void)hipFree(h->a); (void)hipFree(h->b); (void)hipFree(h->c); (void)hipFree(h->tmp); (void)hipFree(h->d_acc);
-    (void)hipFree(h->lat); (void)hipFree(h->ys_chain); (void)hipFree(h->fvals); (void)hipFree(h->fpresent);
-    (void)hipFree(h->gfi_vals); (void)hipFree(h->gfi_present); (void)hipFree(h->gfi_cons); (void)hipFree(h->gfi_cpresent); (void)hipFree(h->d_data);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return MP_OK;
 }

@@ -42,6 +42,7 @@
 
 #include "../../include/modppl_hip.h"
 #include "mp_diag.h"
+#include "mp_hip_own.h"
 #include "mp_linalg.h"
 // models register themselves (mp_models.h, MP_REGISTER_UNFOLD_MODEL): here a registration creates the device factory
 template <class M>
@@ -135,10 +136,10 @@ struct PropagateArgs {
 };
 struct ModelOps {
     int dim_state = 0, dim_obs = 0;
-    void* owned_device_mem = nullptr;   // model constants that do not fit kernel arguments (freed with the model)
+    mp_dev<double> owned_device_mem;    // model constants that do not fit kernel arguments (freed with the model)
     int max_normals = 0;
     bool can_draw = false;   // its k_propagate can make the previous resample's draws itself (lanes of two adjacent slots: the 1024-thread launch shape)
-    virtual ~ModelOps() { if (owned_device_mem) (void)hipFree(owned_device_mem); }
+    virtual ~ModelOps() = default;
     virtual int propagate(const PropagateArgs& a) const = 0;   // -> MP_K1_FORM_* of the kernel it launched
     virtual int n_normals(long long t) const = 0;
     virtual void simulate(u64 n, uint32_t k0, uint32_t k1, int n_steps, const mp_state0& s0, double* states, double* obs, hipStream_t st) const = 0;
@@ -387,15 +388,13 @@ static int32_t make_model(const mp_model_desc* m, std::unique_ptr<ModelOps>& out
         mats.insert(mats.end(), T0.begin(), T0.end());
         mats.insert(mats.end(), Rinv.begin(), Rinv.end());
         mats.insert(mats.end(), TR.begin(), TR.end());
-        double* d_mats = nullptr;
-        HIPCK(hipMalloc(&d_mats, sizeof(double) * mats.size()));
-        if (hipMemcpy(d_mats, mats.data(), sizeof(double) * mats.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d_mats);
+        mp_dev<double> d_mats;
+        HIPCK(mp_hipMalloc(d_mats, mats.size()));
+        if (hipMemcpy(d_mats, mats.data(), sizeof(double) * mats.size(), hipMemcpyHostToDevice) != hipSuccess)
             return mp_fail(MP_ERR_HIP, "MP_MODEL_LGSSM_DENSE: copying the model matrices failed");
-        }
         mp_lgssm_dense<16> k{d_mats, mp_log(detR)};
         auto* ops = new ModelOpsT<mp_lgssm_dense<16>>(k);
-        ops->owned_device_mem = d_mats;
+        ops->owned_device_mem = std::move(d_mats);
         out.reset(ops);
         return MP_OK;
     }
@@ -408,53 +407,55 @@ static int32_t make_model(const mp_model_desc* m, std::unique_ptr<ModelOps>& out
 }
 
 struct TimedLaunch {
-    hipEvent_t start, stop;
+    mp_event start, stop;
     int family;
 };
 
 struct mp_shard_native_state;   // mp_shard_native.h
+struct mp_shard_native_delete { void operator()(mp_shard_native_state* s) const; };
+// Ownership: every field the handle allocates is a holder (mp_hip_own.h); the raw pointers left are views, and say so.  Members are
+// destroyed in reverse order, so the stream comes first: it outlives every buffer, every event and the native exchange's state.
 struct mp_pf {
+    mp_hip_stream stream;
     std::unique_ptr<ModelOps> ops;
-    mp_shard_native_state* native = nullptr;   // buffers and bookkeeping of mp_pf_shard_resample
+    std::unique_ptr<mp_shard_native_state, mp_shard_native_delete> native;   // buffers and bookkeeping of mp_pf_shard_resample
     u64 n = 0, n_global = 0, slot_offset = 0, seed = 0;
     uint32_t flags = 0;
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     int S = 0;
     int nt = 0;  // tiles of this handle (== K1 grid)
     int k3_grid = 0;
     // device buffers
-    double* x[2] = {nullptr, nullptr};
+    mp_dev<double> x[2];
     int cur = 0;
-    double* logw = nullptr;
-    mp_cx* cx = nullptr;
-    unsigned short* guide = nullptr;
-    uint32_t* parent = nullptr;
-    double* tile_m = nullptr;
+    mp_dev<double> logw;
+    mp_dev<mp_cx> cx;
+    mp_dev<unsigned short> guide;
+    mp_dev<uint32_t> parent;
+    double* tile_m = nullptr;    // views: the three parts of tiles_own, or of the caller's buffer after mp_pf_shard_bind_tiles
     u64* tile_W = nullptr;
     u64* tile_W2 = nullptr;
-    mp_dev_scalars* scal = nullptr;
-    double* aos = nullptr;             // staging for read_state
-    mp_dev_scalars* h_scal = nullptr;  // pinned
-    int* h_flag = nullptr;             // host-mapped: the device-side sticky error (mp_dev_scalars::host_flag points here)
-    mp_host_mirror* h_mirror = nullptr;   // host-mapped: L / ESS / log-ML of every fold, and k_peek_level1's answers (mp_pf_kernels.h)
-    mp_host_mirror* d_mirror = nullptr;   // its device address
+    mp_dev<mp_dev_scalars> scal;
+    mp_dev<double> aos;             // staging for read_state
+    mp_pinned<mp_dev_scalars> h_scal;  // pinned
+    mp_pinned<int> h_flag;             // host-mapped: the device-side sticky error (mp_dev_scalars::host_flag points here)
+    mp_pinned<mp_host_mirror> h_mirror;   // host-mapped: L / ESS / log-ML of every fold, and k_peek_level1's answers (mp_pf_kernels.h)
+    mp_host_mirror* d_mirror = nullptr;   // view: its device address
     unsigned long long peek_seq = 0;      // k_peek_level1 launches (and MP_MT_PEEK tails) so far
     bool sync_loop = false;               // the last resample was synchronous (`L = resample()`): the next k_propagate_mt launch peeks for the one to come
     bool peek_valid = false;              // ... and did: peek number peek_seq belongs to the current tile scalars
     int use_mirror = 1;                   // MP_HOST_MIRROR=0: synchronous calls copy mp_dev_scalars back as before (A/B measurements)
     // the draws of a multinomial resample, per output slot (k_draw_slots)
-    u64* dfr_lt = nullptr;              // [n] tile-local target
-    uint32_t* dfr_row = nullptr;        // [n] table row where the forward scan starts
+    mp_dev<u64> dfr_lt;              // [n] tile-local target
+    mp_dev<uint32_t> dfr_row;        // [n] table row where the forward scan starts
     int nchunks = 0;
     int use_deferred = 1;               // MP_DEFERRED_LOOKUPS=0 selects the single-kernel resampler (A/B measurements)
     bool sh_parents_lazy = false;       // ... or in column D of the exchange rows sh_rows / sh_req_slot
     // level-1 table built by the last workgroup of the level-0 launch (mp_tab)
-    mp_k1_tail* k1_tail = nullptr;      // device copy of what k_propagate's last phase needs (update_k1_tail)
-    mp_k1_tail* k1_tail_alt = nullptr;  // the same with cx_alt / guide_alt for cx / guide
-    unsigned short* guide_alt = nullptr; // second guide buffer (swaps with guide together with the row tables)
-    u64* tab_W = nullptr;               // the tile table's copy of tile_W (mp_tab::W)
+    mp_dev<mp_k1_tail> k1_tail;      // device copy of what k_propagate's last phase needs (update_k1_tail)
+    mp_dev<mp_k1_tail> k1_tail_alt;  // the same with cx_alt / guide_alt for cx / guide
+    mp_dev<unsigned short> guide_alt; // second guide buffer (swaps with guide together with the row tables)
+    mp_dev<u64> tab_W;               // the tile table's copy of tile_W (mp_tab::W)
     bool draw_pending = false;          // with `deferred`: not even the draws of the last resample have been made (counter pending_rc);
     uint32_t pending_rc = 0;            // the next k_propagate makes them, or flush_draws() when anything else needs them first
     int pending_scheme = 0;             // (their resampling scheme)
@@ -470,66 +471,66 @@ struct mp_pf {
     // drawing launch), same parents and log-weights, nothing else stored (ensure_lazy).
     int use_lazy = 1;                   // MP_K1_LAZY=0 (diagnostics): every launch stores them
     bool lazy_pending = false;          // logw[] and parent[] are those of an EARLIER launch: lazy_args reproduces the current ones
-    PropagateArgs lazy_args;
-    mp_cx* cx_alt = nullptr;            // second row-table buffer: a k_propagate that looks up deferred draws in cx writes the new table here
+    PropagateArgs lazy_args;            // (views)
+    mp_dev<mp_cx> cx_alt;            // second row-table buffer: a k_propagate that looks up deferred draws in cx writes the new table here
     bool deferred = false;              // the last resample only drew: {dfr_lt, dfr_row}[slot] against the table in cx; x[cur] is the pre-resample state
     bool parents_deferred = false;      // ... and a step has consumed the draws since: its parents are still {dfr_lt, dfr_row} against cx_alt
-    unsigned int* tab_ticket = nullptr;
-    u64* tab_incl = nullptr;
-    double* tab_ratio = nullptr;
-    mp_tab_head* tab_head = nullptr;
+    mp_dev<unsigned int> tab_ticket;
+    mp_dev<u64> tab_incl;
+    mp_dev<double> tab_ratio;
+    mp_dev<mp_tab_head> tab_head;
     int use_k1_table = 1;               // MP_K1_TABLE=0: every k_draw_slots workgroup builds the table itself (A/B measurements)
     // local_table: the level-0 launches of this handle build NO job table (no ticket, no workgroup left behind at the end of every
     // step); a drawing k_propagate builds it per workgroup in LDS from the previous generation's tile scalars, which are therefore
     // double-buffered like the row table (tiles_alt), and k_build_table makes the global one when something else asks for it
     bool local_table = false;
     bool table_fresh = false;           // tab_* (the job's tile table in global memory) describe the current tile scalars
-    u64* tiles_alt = nullptr;           // second [3][nt] tile-scalar buffer
+    mp_dev<u64> tiles_alt;           // second [3][nt] tile-scalar buffer
     bool rows_fresh = false;            // cx / guide / tile_* describe the current log-weights
     bool x_in_rows = false;             // (dim_state 1) the current states are the x0 of the rows of cx; x[cur] is stale (ensure_x)
     // sharded-resample scratch (allocated on first use)
-    unsigned char* sh_dest = nullptr;
-    u64* sh_lt = nullptr;
-    uint32_t* sh_tile = nullptr;
-    uint32_t* sh_req_slot = nullptr;
-    uint32_t* sh_blockcount = nullptr;
-    uint32_t* sh_blockoff = nullptr;
-    long long* sh_counts = nullptr;
+    mp_dev<unsigned char> sh_dest;
+    mp_dev<u64> sh_lt;
+    mp_dev<uint32_t> sh_tile;
+    mp_dev<uint32_t> sh_req_slot;
+    mp_dev<uint32_t> sh_blockcount;
+    mp_dev<uint32_t> sh_blockoff;
+    mp_dev<long long> sh_counts;
     bool ow_placed = false;               // the last count's table launch also placed (self-drawn, equal-split capacity): expand launches nothing
     uint64_t ow_placed_cap = 0;
-    double* ow_placed_send = nullptr;
-    mp_tab_part* sh_tab_part = nullptr;   // [SH_MAX_WORLD] k_shard_table_mw: every rank's {sum T, sum T2}
-    unsigned int* sh_tab_ticket = nullptr;   // counts up by `world` per launch
+    double* ow_placed_send = nullptr;     // view
+    mp_dev<mp_tab_part> sh_tab_part;   // [SH_MAX_WORLD] k_shard_table_mw: every rank's {sum T, sum T2}
+    mp_dev<unsigned int> sh_tab_ticket;   // counts up by `world` per launch
     unsigned int sh_tab_seq = 0;
-    long long* h_counts = nullptr;  // pinned
+    mp_pinned<long long> h_counts;  // pinned
     int sh_world = 0;
     u64 sh_cap = 0;                 // fixed-capacity exchange: request slots per (src, dst) pair
-    double* sh_tm_all = nullptr;    // unpacked gathered tiles
-    u64* sh_tW_all = nullptr;
-    u64* sh_tW2_all = nullptr;
-    double* sh_ratio_all = nullptr;   // and its per-tile (double)W / (double)T
-    u64* sh_incl_all = nullptr;     // the job's tile table (inclusive prefix of T_b), built once per resample by k_shard_table
-    int* sh_overflow = nullptr;
-    unsigned int* sh_done = nullptr;   // [2] tickets of the route / resolve workgroups (the last one writes headers / publishes)
-    u64* tiles_own = nullptr;       // the allocation behind tile_m / tile_W / tile_W2 unless the caller bound its own buffer
-    mp_shard_pub* h_pub = nullptr;  // pinned, host-mapped
-    mp_shard_pub* d_pub = nullptr;  // its device address
-    hipEvent_t ev_resolved = nullptr;
+    mp_dev<double> sh_tm_all;    // unpacked gathered tiles
+    mp_dev<u64> sh_tW_all;
+    mp_dev<u64> sh_tW2_all;
+    mp_dev<double> sh_ratio_all;   // and its per-tile (double)W / (double)T
+    mp_dev<u64> sh_incl_all;     // the job's tile table (inclusive prefix of T_b), built once per resample by k_shard_table
+    mp_dev<int> sh_overflow;
+    mp_dev<unsigned int> sh_done;   // [2] tickets of the route / resolve workgroups (the last one writes headers / publishes)
+    mp_dev<u64> tiles_own;       // the allocation behind tile_m / tile_W / tile_W2 unless the caller bound its own buffer
+    mp_pinned<mp_shard_pub> h_pub;  // pinned, host-mapped
+    mp_shard_pub* d_pub = nullptr;  // view: its device address
+    mp_event ev_resolved;
     bool sh_lazy = false;           // the states of the last sharded resample still sit in the exchange buffer sh_rows, slot i at row sh_req_slot[i]
-    const double* sh_rows = nullptr;
+    const double* sh_rows = nullptr;   // view
     bool sh_recv = false;           // (owner-keeps) the draws of the last resample hold MP_DRAW_RECV entries: rows of sh_rows
     u64 sh_rows_cap = 0;
     bool logw_zero = false;         // log-weights are all zero (after a sharded resample) and the buffer has not been cleared
-    mp_dev_scalars* scal_undo = nullptr;  // the scalars before a fixed-capacity route folded this resample in
+    mp_dev<mp_dev_scalars> scal_undo;  // the scalars before a fixed-capacity route folded this resample in
     // "owner keeps" form: per super-chunk of R * 1024 draws a window of entries (k_shard_own_draw), [ow_nsc][R * 1024]
-    u64* ow_seg_lt = nullptr;             // tile-local target
-    uint32_t* ow_seg_row = nullptr;       // start row of the forward scan
-    uint32_t* ow_sccnt = nullptr;         // own draws per super-chunk, and their exclusive scan
-    uint32_t* ow_base = nullptr;
-    unsigned long long* ow_call = nullptr;   // offspring per rank [SH_MAX_WORLD]
-    mp_owned_plan* ow_plan = nullptr;
-    mp_own_range* ow_range = nullptr;
-    u64* ow_kthr = nullptr;               // [SH_MAX_WORLD] rank boundaries as thresholds on the 52-bit uniforms (multinomial)
+    mp_dev<u64> ow_seg_lt;             // tile-local target
+    mp_dev<uint32_t> ow_seg_row;       // start row of the forward scan
+    mp_dev<uint32_t> ow_sccnt;         // own draws per super-chunk, and their exclusive scan
+    mp_dev<uint32_t> ow_base;
+    mp_dev<unsigned long long> ow_call;   // offspring per rank [SH_MAX_WORLD]
+    mp_dev<mp_owned_plan> ow_plan;
+    mp_dev<mp_own_range> ow_range;
+    mp_dev<u64> ow_kthr;               // [SH_MAX_WORLD] rank boundaries as thresholds on the 52-bit uniforms (multinomial)
     u64 ow_last_cap = 0;                  // capacity of the last mp_pf_shard_owned_expand (0 = exact sizes: nothing can overflow)
     unsigned long long ow_seq = 0;        // owner-keeps resamples planned so far: the plan of number k writes pub->seq = k last
     int ow_nsc = 0, ow_R = 0, ow_wgs = 0;
@@ -540,20 +541,20 @@ struct mp_pf {
     bool ow_self = false;                 // the resample being run (count .. commit) is self-drawn
     bool ow_solo_folded = false;          // (world of one) its scalars have been folded already (a synchronous commit): the next k_propagate must not
     int ow_rank = 0;
-    mp_own_range* ow_range_solo = nullptr;   // {0, n}: a world of one owns every draw
+    mp_dev<mp_own_range> ow_range_solo;   // {0, n}: a world of one owns every draw
     bool draws_lattice = false;           // the draws of the last resample are a lattice's (systematic / stratified)
     int walk_bisect_force = -1;           // MP_WALK_BISECT: 0 = the plain-walk kernels always, 1 = the bisecting ones always, unset = by the rule in launch_propagate
     bool pending_shard = false;           // with draw_pending: the pending draws are a sharded filter's self-drawn ones (world ps_world, rank ps_rank)
     int ps_world = 1, ps_rank = 0;
     bool sharded = false;
     // ancestry record (MP_PF_RECORD_HISTORY): the event log from which `traces[i].retv` is rebuilt
-    struct HistEvent { int kind; void* buf; };  // kind 0: states after an Unfold step ([n][d] f64); 1: parents of a resample ([n] u32)
+    struct HistEvent { int kind; void* buf; };  // (buf: view into a slab) kind 0: states after an Unfold step ([n][d] f64); 1: parents of a resample ([n] u32)
     std::vector<HistEvent> hist;
     // the event buffers come out of slabs that grow geometrically, so a step or a resample does not call hipMalloc
-    std::vector<void*> hist_slabs;
-    unsigned char* hist_slab_cur = nullptr;
+    std::vector<mp_dev<unsigned char>> hist_slabs;
+    unsigned char* hist_slab_cur = nullptr;   // view
     size_t hist_slab_left = 0, hist_slab_next = 0;
-    mp_hist_event* d_hist_events = nullptr;   // device copy of the log for k_trajectories
+    mp_dev<mp_hist_event> d_hist_events;   // device copy of the log for k_trajectories
     size_t d_hist_events_cap = 0;
     // host-side filter state
     long long t = 0;  // Unfold steps taken (trace.args.0)
@@ -562,9 +563,9 @@ struct mp_pf {
     // timing
     bool timing = false;
     std::vector<TimedLaunch> timed;
-    std::vector<hipEvent_t> event_pool;
+    std::vector<mp_event> event_pool;
     int last_k1_form = -1;                          // MP_K1_FORM_* of the last k_propagate-family launch
-    hipEvent_t region_ev[2] = {nullptr, nullptr};   // mp_pf_region_begin / _end
+    mp_event region_ev[2];                          // mp_pf_region_begin / _end
     bool region_open = false;
     uint64_t region_launches = 0;
     double fam_ms[MP_K_COUNT] = {0, 0, 0, 0};
@@ -586,30 +587,30 @@ static mp_tab tab_of(const mp_pf* h) {
 static int32_t update_k1_tail(mp_pf* h) {   // after anything that changes one of these pointers
     mp_k1_tail t;
     t.cx = h->cx; t.guide = h->guide; t.tile_m = h->tile_m; t.tile_W = h->tile_W; t.tile_W2 = h->tile_W2; t.tab = tab_of(h);
-    if (!h->k1_tail) HIPCK(hipMalloc(&h->k1_tail, sizeof(mp_k1_tail)));
+    if (!h->k1_tail) HIPCK(mp_hipMalloc(h->k1_tail, 1));
     HIPCK(hipMemcpyAsync(h->k1_tail, &t, sizeof(t), hipMemcpyHostToDevice, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));   // `t` is a stack object
     if (h->cx_alt) {
         t.cx = h->cx_alt;
         t.guide = h->guide_alt;
         if (h->local_table) {   // (the launch that draws reads the old generation's tile scalars while it writes the new one's)
-            t.tile_m = reinterpret_cast<double*>(h->tiles_alt); t.tile_W = h->tiles_alt + h->nt; t.tile_W2 = h->tiles_alt + 2 * (size_t)h->nt;
+            t.tile_m = reinterpret_cast<double*>(h->tiles_alt.get()); t.tile_W = h->tiles_alt + h->nt; t.tile_W2 = h->tiles_alt + 2 * (size_t)h->nt;
         }
-        if (!h->k1_tail_alt) HIPCK(hipMalloc(&h->k1_tail_alt, sizeof(mp_k1_tail)));
+        if (!h->k1_tail_alt) HIPCK(mp_hipMalloc(h->k1_tail_alt, 1));
         HIPCK(hipMemcpyAsync(h->k1_tail_alt, &t, sizeof(t), hipMemcpyHostToDevice, h->stream));
         HIPCK(hipStreamSynchronize(h->stream));
     }
     return MP_OK;
 }
 
-static hipEvent_t get_event(mp_pf* h) {
+static mp_event get_event(mp_pf* h) {
+    mp_event e;
     if (!h->event_pool.empty()) {
-        hipEvent_t e = h->event_pool.back();
+        e = std::move(h->event_pool.back());
         h->event_pool.pop_back();
-        return e;
+    } else {
+        (void)mp_hipEventCreate(e);
     }
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
     return e;
 }
 struct LaunchTimer {
@@ -627,7 +628,7 @@ struct LaunchTimer {
     ~LaunchTimer() {
         if (on) {
             (void)hipEventRecord(tl.stop, h->stream);
-            h->timed.push_back(tl);
+            h->timed.push_back(std::move(tl));
         }
     }
 };
@@ -639,8 +640,8 @@ static int32_t drain_timing(mp_pf* h) {
         HIPCK(hipEventElapsedTime(&ms, tl.start, tl.stop));
         h->fam_ms[tl.family] += (double)ms;
         h->fam_launches[tl.family] += 1;
-        h->event_pool.push_back(tl.start);
-        h->event_pool.push_back(tl.stop);
+        h->event_pool.push_back(std::move(tl.start));
+        h->event_pool.push_back(std::move(tl.stop));
     }
     h->timed.clear();
     return MP_OK;
@@ -748,10 +749,10 @@ static int32_t hist_alloc(mp_pf* h, size_t bytes, void** out) {
     if (h->hist_slab_left < bytes) {
         size_t want = h->hist_slab_next ? h->hist_slab_next : 8 * bytes;
         if (want < bytes) want = bytes;
-        void* slab = nullptr;
-        HIPCK(hipMalloc(&slab, want));
-        h->hist_slabs.push_back(slab);
-        h->hist_slab_cur = static_cast<unsigned char*>(slab);
+        mp_dev<unsigned char> slab;
+        HIPCK(mp_hipMalloc(slab, want));
+        h->hist_slab_cur = slab;
+        h->hist_slabs.push_back(std::move(slab));
         h->hist_slab_left = want;
         h->hist_slab_next = 2 * want;
     }
@@ -789,7 +790,7 @@ static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs
     a.tile_m = h->tile_m; a.tile_W = h->tile_W; a.tile_W2 = h->tile_W2;
     a.tile_m_new = h->tile_m; a.tile_W_new = h->tile_W; a.tile_W2_new = h->tile_W2;
     if (h->deferred && h->local_table && h->tiles_alt) {   // (what k1_tail_alt says: update_k1_tail)
-        a.tile_m_new = reinterpret_cast<double*>(h->tiles_alt); a.tile_W_new = h->tiles_alt + h->nt; a.tile_W2_new = h->tiles_alt + 2 * (size_t)h->nt;
+        a.tile_m_new = reinterpret_cast<double*>(h->tiles_alt.get()); a.tile_W_new = h->tiles_alt + h->nt; a.tile_W2_new = h->tiles_alt + 2 * (size_t)h->nt;
     }
     // Long row walks (collapsed weights: mp_resolve_draws' BISECT) — which instantiation looks the draws up.  One-double models: always
     // the long-walk one (with MP_WALK_LINEAR = 12 it measures the same as the plain walk on healthy weights — 37.3 us either way,
@@ -842,7 +843,7 @@ static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs
     a.aux.tab = tab_of(h);
     a.aux.x_rows = 0;
     if (h->ops->dim_state == 1 && h->x_in_rows && !h->deferred && !h->sh_lazy) {   // a plain step: the previous states are the x0 of the current rows
-        a.x_in = reinterpret_cast<const double*>(h->cx);
+        a.x_in = reinterpret_cast<const double*>(h->cx.get());
         a.aux.x_rows = 1;
     }
     a.tail = h->deferred ? h->k1_tail_alt : h->k1_tail;
@@ -858,12 +859,12 @@ static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs
     h->peek_valid = want_peek && h->last_k1_form == MP_K1_FORM_TWO_TILES;
     if (h->peek_valid) h->peek_seq += 1;
     if (h->deferred) {   // the fresh table is the current one from here on; the old one stays intact for mp_pf_read_parents
-        std::swap(h->cx, h->cx_alt);
-        std::swap(h->guide, h->guide_alt);
-        std::swap(h->k1_tail, h->k1_tail_alt);
+        h->cx.swap(h->cx_alt);
+        h->guide.swap(h->guide_alt);
+        h->k1_tail.swap(h->k1_tail_alt);
         if (h->local_table) {
-            std::swap(h->tiles_own, h->tiles_alt);
-            h->tile_m = reinterpret_cast<double*>(h->tiles_own); h->tile_W = h->tiles_own + h->nt; h->tile_W2 = h->tiles_own + 2 * (size_t)h->nt;
+            h->tiles_own.swap(h->tiles_alt);
+            h->tile_m = reinterpret_cast<double*>(h->tiles_own.get()); h->tile_W = h->tiles_own + h->nt; h->tile_W2 = h->tiles_own + 2 * (size_t)h->nt;
         }
         h->draw_pending = false;
         h->pending_shard = false;
@@ -957,12 +958,8 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
         return mp_fail(MP_ERR_HIP, "no HIP device visible: the gfx950 path has no CPU fallback");
     }
     HIPCK(hipSetDevice(device));
-    if (stream) {
-        h->stream = (hipStream_t)stream;
-    } else {
-        HIPCK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
+    if (stream) h->stream.borrow((hipStream_t)stream);
+    else HIPCK(h->stream.create(hipStreamNonBlocking));
     const u64 n = h->n;
     const int d = h->ops->dim_state;
     h->nt = (int)((n + TILE - 1) / TILE);
@@ -996,30 +993,30 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
         h->local_table = !h->sharded && h->use_k1_table && h->use_fused_draws && h->use_deferred && h->ops->can_draw && h->nt <= 2048 &&
                          !(h->flags & MP_PF_RECORD_HISTORY) && !(env && env[0] == '0');
     }
-    HIPCK(hipMalloc(&h->x[0], sizeof(double) * n * d));
-    HIPCK(hipMalloc(&h->x[1], sizeof(double) * n * d));
-    HIPCK(hipMalloc(&h->logw, sizeof(double) * n));
-    HIPCK(hipMalloc(&h->cx, sizeof(mp_cx) * (size_t)h->nt * TILE));
-    HIPCK(hipMalloc(&h->guide, sizeof(unsigned short) * (size_t)h->nt * GUIDE_N));
-    HIPCK(hipMalloc(&h->parent, sizeof(uint32_t) * n));
-    HIPCK(hipMalloc(&h->tiles_own, sizeof(u64) * 3 * h->nt));   // packed [3][nt]: m (f64 bits), W, W2 — the unit the shards all-gather
-    h->tile_m = reinterpret_cast<double*>(h->tiles_own);
+    HIPCK(mp_hipMalloc(h->x[0], n * d));
+    HIPCK(mp_hipMalloc(h->x[1], n * d));
+    HIPCK(mp_hipMalloc(h->logw, n));
+    HIPCK(mp_hipMalloc(h->cx, (size_t)h->nt * TILE));
+    HIPCK(mp_hipMalloc(h->guide, (size_t)h->nt * GUIDE_N));
+    HIPCK(mp_hipMalloc(h->parent, n));
+    HIPCK(mp_hipMalloc(h->tiles_own, 3 * h->nt));   // packed [3][nt]: m (f64 bits), W, W2 — the unit the shards all-gather
+    h->tile_m = reinterpret_cast<double*>(h->tiles_own.get());
     h->tile_W = h->tiles_own + h->nt;
     h->tile_W2 = h->tiles_own + 2 * (size_t)h->nt;
-    HIPCK(hipMalloc(&h->scal, sizeof(mp_dev_scalars)));
+    HIPCK(mp_hipMalloc(h->scal, 1));
     if (!h->sharded) {
-        HIPCK(hipMalloc(&h->tab_ticket, 64));   // a line of its own
+        HIPCK(mp_hipMalloc(h->tab_ticket, 64 / sizeof(unsigned int)));   // a line of its own
         HIPCK(hipMemsetAsync(h->tab_ticket, 0, 64, h->stream));
-        HIPCK(hipMalloc(&h->tab_incl, sizeof(u64) * h->nt));
-        HIPCK(hipMalloc(&h->tab_ratio, sizeof(double) * h->nt));
-        HIPCK(hipMalloc(&h->tab_head, sizeof(mp_tab_head)));
-        HIPCK(hipMalloc(&h->tab_W, sizeof(u64) * h->nt));
+        HIPCK(mp_hipMalloc(h->tab_incl, h->nt));
+        HIPCK(mp_hipMalloc(h->tab_ratio, h->nt));
+        HIPCK(mp_hipMalloc(h->tab_head, 1));
+        HIPCK(mp_hipMalloc(h->tab_W, h->nt));
     }
-    HIPCK(hipMalloc(&h->aos, sizeof(double) * n));   // scratch for importance sampling's normalised log-weights
-    HIPCK(hipHostMalloc(&h->h_scal, sizeof(mp_dev_scalars)));
+    HIPCK(mp_hipMalloc(h->aos, n));   // scratch for importance sampling's normalised log-weights
+    HIPCK(mp_hipHostMalloc(h->h_scal, 1));
     if (!h->sharded) {   // (sharded handles resample through the mp_pf_shard_* phases)
-        HIPCK(hipMalloc(&h->dfr_lt, sizeof(u64) * (size_t)h->nchunks * DRAW_CHUNK));
-        HIPCK(hipMalloc(&h->dfr_row, sizeof(uint32_t) * (size_t)h->nchunks * DRAW_CHUNK));
+        HIPCK(mp_hipMalloc(h->dfr_lt, (size_t)h->nchunks * DRAW_CHUNK));
+        HIPCK(mp_hipMalloc(h->dfr_row, (size_t)h->nchunks * DRAW_CHUNK));
     }
     // tile tables above 64 KiB of LDS need the limit raised once per kernel
     {
@@ -1041,7 +1038,7 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
     HIPCK(hipMemsetAsync(h->x[1], 0, sizeof(double) * n * d, h->stream));
     HIPCK(hipMemsetAsync(h->logw, 0, sizeof(double) * n, h->stream));
     HIPCK(hipMemsetAsync(h->parent, 0, sizeof(uint32_t) * n, h->stream));
-    HIPCK(hipHostMalloc(&h->h_flag, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCK(mp_hipHostMalloc(h->h_flag, 1, hipHostMallocMapped | hipHostMallocCoherent));
     *h->h_flag = 0;
     mp_dev_scalars init{};
     init.ess_stale = 1.0 / (double)h->n_global;  // exp(-logsumexp(zeros)) before any resample
@@ -1051,7 +1048,7 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
         if (env && env[0] == '0') h->use_mirror = 0;
     }
     if (!h->sharded && h->use_mirror) {   // (sharded handles fold, undo and re-fold through mp_pf_shard_*: they keep the copy)
-        HIPCK(hipHostMalloc(&h->h_mirror, sizeof(mp_host_mirror), hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCK(mp_hipHostMalloc(h->h_mirror, 1, hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(h->h_mirror, 0, sizeof(mp_host_mirror));
         h->h_mirror->ess_stale = init.ess_stale;
         HIPCK(hipHostGetDevicePointer((void**)&h->d_mirror, h->h_mirror, 0));
@@ -1180,9 +1177,9 @@ int32_t mp_pf_resample(mp_pf* h, int32_t scheme, double* log_total_weight) {
         // draws only: the lookups are done by whoever consumes the parents — the next k_propagate, under its arithmetic, or
         // k_resolve_slots when the host asks first
         if (!h->cx_alt) {
-            HIPCK(hipMalloc(&h->cx_alt, sizeof(mp_cx) * (size_t)h->nt * TILE));
-            HIPCK(hipMalloc(&h->guide_alt, sizeof(unsigned short) * (size_t)h->nt * GUIDE_N));
-            if (h->local_table) HIPCK(hipMalloc(&h->tiles_alt, sizeof(u64) * 3 * h->nt));
+            HIPCK(mp_hipMalloc(h->cx_alt, (size_t)h->nt * TILE));
+            HIPCK(mp_hipMalloc(h->guide_alt, (size_t)h->nt * GUIDE_N));
+            if (h->local_table) HIPCK(mp_hipMalloc(h->tiles_alt, 3 * h->nt));
             int32_t rct = update_k1_tail(h);
             if (rct != MP_OK) return rct;
         }
@@ -1490,39 +1487,36 @@ int32_t mp_pf_shard_query(mp_pf* h, const double* d_tm_all, const uint64_t* d_tW
 static int32_t shard_scratch(mp_pf* h, int world, u64 cap) {
     const int nblk = (int)((h->n + SH_THREADS - 1) / SH_THREADS);
     if (h->sh_dest && h->sh_world >= world && h->sh_cap >= cap && h->sh_tm_all) return MP_OK;
-    (void)hipFree(h->sh_dest); (void)hipFree(h->sh_lt); (void)hipFree(h->sh_tile); (void)hipFree(h->sh_req_slot); (void)hipFree(h->sh_blockcount);
-    (void)hipFree(h->sh_blockoff); (void)hipFree(h->sh_counts); (void)hipFree(h->sh_tm_all); (void)hipFree(h->sh_tW_all); (void)hipFree(h->sh_tW2_all); (void)hipFree(h->sh_incl_all); (void)hipFree(h->sh_ratio_all);
-    (void)hipFree(h->sh_overflow); (void)hipFree(h->sh_done); (void)hipFree(h->sh_tab_part); (void)hipFree(h->sh_tab_ticket);
-    if (h->h_counts) (void)hipHostFree(h->h_counts);
+    h->sh_world = 0;   // (until every buffer below exists; each allocation releases what its holder held)
     const u64 slots = std::max<u64>(h->n, (u64)world * SH_BINS * cap);
-    HIPCK(hipMalloc(&h->sh_dest, h->n));
-    HIPCK(hipMalloc(&h->sh_lt, sizeof(u64) * h->n));
-    HIPCK(hipMalloc(&h->sh_tile, sizeof(uint32_t) * h->n));
-    HIPCK(hipMalloc(&h->sh_req_slot, sizeof(uint32_t) * slots));
+    HIPCK(mp_hipMalloc(h->sh_dest, h->n));
+    HIPCK(mp_hipMalloc(h->sh_lt, h->n));
+    HIPCK(mp_hipMalloc(h->sh_tile, h->n));
+    HIPCK(mp_hipMalloc(h->sh_req_slot, slots));
     HIPCK(hipMemsetAsync(h->sh_req_slot, 0, sizeof(uint32_t) * slots, h->stream));   // never an out-of-range row index, whatever path leaves it unwritten
-    HIPCK(hipMalloc(&h->sh_blockcount, sizeof(uint32_t) * (size_t)nblk * world));
-    HIPCK(hipMalloc(&h->sh_blockoff, sizeof(uint32_t) * (size_t)nblk * world));
-    HIPCK(hipMalloc(&h->sh_counts, sizeof(long long) * SH_MAX_KEYS));
-    HIPCK(hipMalloc(&h->sh_tm_all, sizeof(double) * (size_t)h->nt * world));
-    HIPCK(hipMalloc(&h->sh_tW_all, sizeof(u64) * (size_t)h->nt * world));
-    HIPCK(hipMalloc(&h->sh_tW2_all, sizeof(u64) * (size_t)h->nt * world));
-    HIPCK(hipMalloc(&h->sh_incl_all, sizeof(u64) * (size_t)h->nt * world));
-    HIPCK(hipMalloc(&h->sh_ratio_all, sizeof(double) * (size_t)h->nt * world));
-    HIPCK(hipMalloc(&h->sh_overflow, sizeof(int)));
-    HIPCK(hipMalloc(&h->sh_done, 2 * sizeof(unsigned int)));
-    HIPCK(hipMalloc(&h->sh_tab_part, sizeof(mp_tab_part) * SH_MAX_WORLD));
-    HIPCK(hipMalloc(&h->sh_tab_ticket, sizeof(unsigned int)));
+    HIPCK(mp_hipMalloc(h->sh_blockcount, (size_t)nblk * world));
+    HIPCK(mp_hipMalloc(h->sh_blockoff, (size_t)nblk * world));
+    HIPCK(mp_hipMalloc(h->sh_counts, SH_MAX_KEYS));
+    HIPCK(mp_hipMalloc(h->sh_tm_all, (size_t)h->nt * world));
+    HIPCK(mp_hipMalloc(h->sh_tW_all, (size_t)h->nt * world));
+    HIPCK(mp_hipMalloc(h->sh_tW2_all, (size_t)h->nt * world));
+    HIPCK(mp_hipMalloc(h->sh_incl_all, (size_t)h->nt * world));
+    HIPCK(mp_hipMalloc(h->sh_ratio_all, (size_t)h->nt * world));
+    HIPCK(mp_hipMalloc(h->sh_overflow, 1));
+    HIPCK(mp_hipMalloc(h->sh_done, 2));
+    HIPCK(mp_hipMalloc(h->sh_tab_part, SH_MAX_WORLD));
+    HIPCK(mp_hipMalloc(h->sh_tab_ticket, 1));
     HIPCK(hipMemsetAsync(h->sh_tab_ticket, 0, sizeof(unsigned int), h->stream));
     h->sh_tab_seq = 0;
     HIPCK(hipMemsetAsync(h->sh_done, 0, 2 * sizeof(unsigned int), h->stream));
-    if (!h->scal_undo) HIPCK(hipMalloc(&h->scal_undo, sizeof(mp_dev_scalars)));
+    if (!h->scal_undo) HIPCK(mp_hipMalloc(h->scal_undo, 1));
     HIPCK(hipMemsetAsync(h->sh_overflow, 0, sizeof(int), h->stream));
-    HIPCK(hipHostMalloc(&h->h_counts, sizeof(long long) * SH_MAX_WORLD));
+    HIPCK(mp_hipHostMalloc(h->h_counts, SH_MAX_WORLD));
     if (!h->h_pub) {
-        HIPCK(hipHostMalloc(&h->h_pub, sizeof(mp_shard_pub), hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCK(mp_hipHostMalloc(h->h_pub, 1, hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(h->h_pub, 0, sizeof(mp_shard_pub));
         HIPCK(hipHostGetDevicePointer((void**)&h->d_pub, h->h_pub, 0));
-        HIPCK(hipEventCreateWithFlags(&h->ev_resolved, hipEventDisableTiming));
+        HIPCK(mp_hipEventCreate(h->ev_resolved, hipEventDisableTiming));
     }
     h->sh_world = world;
     h->sh_cap = cap;
@@ -1599,7 +1593,7 @@ int32_t mp_pf_shard_route_fixed(mp_pf* h, int32_t scheme, const uint64_t* d_tile
         const int nblk_f = (int)((h->n + SH_THREADS * SHF_ITEMS - 1) / (SH_THREADS * SHF_ITEMS));
         hipLaunchKernelGGL(k_shard_route_fused, dim3(nblk_f), dim3(SH_THREADS), 0, h->stream, h->n, h->n_global, h->slot_offset, (uint32_t)h->seed,
                            (uint32_t)(h->seed >> 32), h->resample_count, (int)scheme, (const u64*)h->sh_incl_all, (const u64*)h->sh_tW_all, (const double*)h->sh_ratio_all,
-                           nt_all, h->nt, world, (u64)capacity, (unsigned long long*)h->sh_counts, (u64*)d_req_out, h->sh_req_slot, h->sh_done,
+                           nt_all, h->nt, world, (u64)capacity, (unsigned long long*)h->sh_counts.get(), (u64*)d_req_out, h->sh_req_slot, h->sh_done,
                            h->sh_overflow);
     }
     return check_launch("shard_route_fixed kernels");
@@ -1663,15 +1657,6 @@ int32_t mp_pf_shard_commit_fixed(mp_pf* h, const double* d_rows_in, double* log_
 }
 
 // ---- "owner keeps" form: offspring stay with the rank that owns their parent; only the surplus travels ----
-static void owned_free(mp_pf* h) {
-    (void)hipFree(h->ow_seg_lt); (void)hipFree(h->ow_seg_row);
-    (void)hipFree(h->ow_sccnt); (void)hipFree(h->ow_base); (void)hipFree(h->ow_call); (void)hipFree(h->ow_plan);
-    (void)hipFree(h->ow_range); (void)hipFree(h->ow_kthr); (void)hipFree(h->ow_range_solo);
-    h->ow_range_solo = nullptr;
-    h->ow_kthr = nullptr;
-    h->ow_seg_lt = nullptr; h->ow_seg_row = nullptr;
-    h->ow_sccnt = nullptr; h->ow_base = nullptr; h->ow_call = nullptr; h->ow_plan = nullptr; h->ow_range = nullptr;
-}
 // super-chunk shape of one resample: the multinomial draws of a rank are spread over all N draws, so a workgroup takes
 // min(world, 4) rounds of 1024 to collect ~1024 own ones; under a lattice scheme a rank's own draws are one contiguous range
 static void owned_shape(mp_pf* h, int world, int scheme) {
@@ -1682,42 +1667,40 @@ static void owned_shape(mp_pf* h, int world, int scheme) {
 }
 static int32_t owned_scratch(mp_pf* h, int world) {
     if (h->ow_seg_lt && h->ow_world == world) return MP_OK;
-    if (h->ow_seg_lt) {
-        HIPCK(hipStreamSynchronize(h->stream));
-        owned_free(h);
-    }
+    if (h->ow_seg_lt) HIPCK(hipStreamSynchronize(h->stream));   // (each allocation below releases what its holder held)
+    h->ow_world = 0;
     // Windows cover every draw of the job (a rank may own any of them), touched only where this rank owns draws:
     // 16 B x n_global of address space per rank, ~16 B x n_local of it used per resample.
     // (sized for single-round super-chunks, the most there can be; owned_shape() picks the rounds per resampling scheme)
     const int nsc1 = (int)((h->n_global + OWN_ROUND - 1) / OWN_ROUND);
     const size_t ent = (size_t)nsc1 * OWN_ROUND;
     h->ow_nsc = nsc1;
-    HIPCK(hipMalloc(&h->ow_seg_lt, sizeof(u64) * (world == 1 ? 2 : ent)));        // (a world of one writes its draws straight into the slot-order arrays)
-    HIPCK(hipMalloc(&h->ow_seg_row, sizeof(uint32_t) * (world == 1 ? 2 : ent)));
+    HIPCK(mp_hipMalloc(h->ow_seg_lt, (world == 1 ? 2 : ent)));        // (a world of one writes its draws straight into the slot-order arrays)
+    HIPCK(mp_hipMalloc(h->ow_seg_row, (world == 1 ? 2 : ent)));
     // what the next k_propagate (or k_resolve_slots) looks the kept offspring up from, and the second table it writes meanwhile:
     // the deferred-lookup machinery of the unsharded resample
     if (!h->dfr_lt) {
-        HIPCK(hipMalloc(&h->dfr_lt, sizeof(u64) * (size_t)h->nchunks * DRAW_CHUNK));
-        HIPCK(hipMalloc(&h->dfr_row, sizeof(uint32_t) * (size_t)h->nchunks * DRAW_CHUNK));
+        HIPCK(mp_hipMalloc(h->dfr_lt, (size_t)h->nchunks * DRAW_CHUNK));
+        HIPCK(mp_hipMalloc(h->dfr_row, (size_t)h->nchunks * DRAW_CHUNK));
     }
     if (!h->cx_alt) {
-        HIPCK(hipMalloc(&h->cx_alt, sizeof(mp_cx) * (size_t)h->nt * TILE));
-        HIPCK(hipMalloc(&h->guide_alt, sizeof(unsigned short) * (size_t)h->nt * GUIDE_N));
-        if (h->local_table) HIPCK(hipMalloc(&h->tiles_alt, sizeof(u64) * 3 * h->nt));
+        HIPCK(mp_hipMalloc(h->cx_alt, (size_t)h->nt * TILE));
+        HIPCK(mp_hipMalloc(h->guide_alt, (size_t)h->nt * GUIDE_N));
+        if (h->local_table) HIPCK(mp_hipMalloc(h->tiles_alt, 3 * h->nt));
         int32_t rct = update_k1_tail(h);
         if (rct != MP_OK) return rct;
     }
-    HIPCK(hipMalloc(&h->ow_sccnt, sizeof(uint32_t) * (size_t)h->ow_nsc));
-    HIPCK(hipMalloc(&h->ow_base, sizeof(uint32_t) * (size_t)h->ow_nsc));
-    HIPCK(hipMalloc(&h->ow_call, sizeof(unsigned long long) * SH_MAX_WORLD));
-    HIPCK(hipMalloc(&h->ow_plan, sizeof(mp_owned_plan)));
-    HIPCK(hipMalloc(&h->ow_range, sizeof(mp_own_range)));
-    HIPCK(hipMalloc(&h->ow_kthr, sizeof(u64) * SH_MAX_WORLD));
+    HIPCK(mp_hipMalloc(h->ow_sccnt, (size_t)h->ow_nsc));
+    HIPCK(mp_hipMalloc(h->ow_base, (size_t)h->ow_nsc));
+    HIPCK(mp_hipMalloc(h->ow_call, SH_MAX_WORLD));
+    HIPCK(mp_hipMalloc(h->ow_plan, 1));
+    HIPCK(mp_hipMalloc(h->ow_range, 1));
+    HIPCK(mp_hipMalloc(h->ow_kthr, SH_MAX_WORLD));
     HIPCK(hipMemsetAsync(h->ow_call, 0, sizeof(unsigned long long) * SH_MAX_WORLD, h->stream));
     HIPCK(hipMemsetAsync(h->ow_plan, 0, sizeof(mp_owned_plan), h->stream));
     if (world == 1) {   // what k_shard_own_plan would find, every time (it is not launched in a world of one)
         const mp_own_range all{0ull, h->n};
-        HIPCK(hipMalloc(&h->ow_range_solo, sizeof(mp_own_range)));
+        HIPCK(mp_hipMalloc(h->ow_range_solo, 1));
         HIPCK(hipMemcpyAsync(h->ow_range_solo, &all, sizeof(all), hipMemcpyHostToDevice, h->stream));
         std::vector<uint32_t> base((size_t)nsc1);
         for (int k = 0; k < nsc1; ++k) base[(size_t)k] = (uint32_t)((u64)k * OWN_ROUND);
@@ -2063,21 +2046,20 @@ int32_t mp_pf_read_trajectories(mp_pf* h, uint64_t first, uint64_t count, double
     std::vector<mp_hist_event> ev(h->hist.size());
     for (size_t e = 0; e < h->hist.size(); ++e) { ev[e].buf = h->hist[e].buf; ev[e].kind = h->hist[e].kind; ev[e].pad = 0; }
     if (h->d_hist_events_cap < ev.size()) {
-        (void)hipFree(h->d_hist_events);
-        h->d_hist_events = nullptr;
-        h->d_hist_events_cap = std::max<size_t>(64, 2 * ev.size());
-        HIPCK(hipMalloc(&h->d_hist_events, sizeof(mp_hist_event) * h->d_hist_events_cap));
+        h->d_hist_events_cap = 0;
+        const size_t cap = std::max<size_t>(64, 2 * ev.size());
+        HIPCK(mp_hipMalloc(h->d_hist_events, cap));
+        h->d_hist_events_cap = cap;
     }
     HIPCK(hipMemcpyAsync(h->d_hist_events, ev.data(), sizeof(mp_hist_event) * ev.size(), hipMemcpyHostToDevice, h->stream));
-    double* d_out = nullptr;
+    mp_dev<double> d_out;
     const size_t bytes = sizeof(double) * (size_t)count * (size_t)T * (size_t)d;
-    HIPCK(hipMalloc(&d_out, bytes));
+    HIPCK(mp_hipMalloc(d_out, (size_t)count * (size_t)T * (size_t)d));
     hipLaunchKernelGGL(k_trajectories, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, (u64)first, (u64)count, d, T, (int)ev.size(),
-                       (const mp_hist_event*)h->d_hist_events, d_out);
+                       (const mp_hist_event*)h->d_hist_events, d_out.get());
     hipError_t e1 = hipGetLastError();
     if (e1 == hipSuccess) e1 = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, h->stream);
     if (e1 == hipSuccess) e1 = hipStreamSynchronize(h->stream);   // (ev / d_out stay alive until here)
-    (void)hipFree(d_out);
     if (e1 != hipSuccess) return mp_fail(MP_ERR_HIP, std::string("mp_pf_read_trajectories: ") + hipGetErrorString(e1));
     return MP_OK;
 }
@@ -2150,8 +2132,8 @@ int32_t mp_pf_region_begin(mp_pf* h) {
     if (!h) return mp_fail(MP_ERR_INVALID_ARG, "null handle");
     HIPCK(hipSetDevice(h->device));
     if (!h->region_ev[0]) {
-        HIPCK(hipEventCreate(&h->region_ev[0]));
-        HIPCK(hipEventCreate(&h->region_ev[1]));
+        HIPCK(mp_hipEventCreate(h->region_ev[0]));
+        HIPCK(mp_hipEventCreate(h->region_ev[1]));
     }
     h->region_launches = 0;
     HIPCK(hipEventRecord(h->region_ev[0], h->stream));
@@ -2173,38 +2155,10 @@ int32_t mp_pf_region_end(mp_pf* h, double* elapsed_ms, uint64_t* propagate_launc
     return MP_OK;
 }
 
-static void shard_native_free(mp_shard_native_state* s);   // mp_shard_native.h
 int32_t mp_pf_destroy(mp_pf* h) {
     if (!h) return MP_OK;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    shard_native_free(h->native);
-    for (auto& tl : h->timed) {
-        (void)hipEventDestroy(tl.start);
-        (void)hipEventDestroy(tl.stop);
-    }
-    for (auto e : h->event_pool) (void)hipEventDestroy(e);
-    for (auto e : h->region_ev) if (e) (void)hipEventDestroy(e);
-    for (void* slab : h->hist_slabs) (void)hipFree(slab);
-    (void)hipFree(h->d_hist_events);
-    (void)hipFree(h->x[0]); (void)hipFree(h->x[1]); (void)hipFree(h->logw); (void)hipFree(h->cx); (void)hipFree(h->cx_alt); (void)hipFree(h->k1_tail_alt); (void)hipFree(h->guide);
-    (void)hipFree(h->guide_alt); (void)hipFree(h->tab_W);
-    (void)hipFree(h->parent); (void)hipFree(h->tiles_own); (void)hipFree(h->tiles_alt); (void)hipFree(h->scal);
-    (void)hipFree(h->aos);
-    (void)hipFree(h->k1_tail);
-    (void)hipFree(h->tab_ticket); (void)hipFree(h->tab_incl); (void)hipFree(h->tab_ratio); (void)hipFree(h->tab_head);
-    (void)hipFree(h->dfr_lt); (void)hipFree(h->dfr_row);
-    (void)hipFree(h->sh_dest); (void)hipFree(h->sh_lt); (void)hipFree(h->sh_tile); (void)hipFree(h->sh_req_slot); (void)hipFree(h->sh_blockcount);
-    (void)hipFree(h->sh_blockoff); (void)hipFree(h->sh_counts); (void)hipFree(h->sh_tm_all); (void)hipFree(h->sh_tW_all); (void)hipFree(h->sh_tW2_all); (void)hipFree(h->sh_incl_all); (void)hipFree(h->sh_ratio_all);
-    (void)hipFree(h->sh_overflow); (void)hipFree(h->sh_done); (void)hipFree(h->scal_undo);
-    owned_free(h);
-    if (h->h_counts) (void)hipHostFree(h->h_counts);
-    if (h->h_pub) (void)hipHostFree(h->h_pub);
-    if (h->ev_resolved) (void)hipEventDestroy(h->ev_resolved);
-    (void)hipHostFree(h->h_scal);
-    if (h->h_flag) (void)hipHostFree(h->h_flag);
-    if (h->h_mirror) (void)hipHostFree(h->h_mirror);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return MP_OK;
 }
@@ -2227,16 +2181,15 @@ int32_t mp_unfold_simulate(const mp_model_desc* model, const double* args0, int3
     }
     HIPCK(hipSetDevice(device));
     const size_t nx = (size_t)n * n_steps * ops->dim_state, ny = (size_t)n * n_steps * ops->dim_obs;
-    double *dx = nullptr, *dy = nullptr;
-    HIPCK(hipMalloc(&dx, sizeof(double) * nx));
-    if (hipMalloc(&dy, sizeof(double) * ny) != hipSuccess) { (void)hipFree(dx); return mp_fail(MP_ERR_HIP, "hipMalloc failed"); }
+    mp_dev<double> dx, dy;
+    HIPCK(mp_hipMalloc(dx, nx));
+    if (mp_hipMalloc(dy, ny) != hipSuccess) return mp_fail(MP_ERR_HIP, "hipMalloc failed");
     mp_state0 s0{};
     for (int j = 0; j < MP_MAX_STATE; ++j) s0.v[j] = (args0 && j < ops->dim_state) ? args0[j] : 0.;
     ops->simulate(n, (uint32_t)seed, (uint32_t)(seed >> 32), n_steps, s0, dx, dy, nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(states_out, dx, sizeof(double) * nx, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(obs_out, dy, sizeof(double) * ny, hipMemcpyDeviceToHost);
-    (void)hipFree(dx); (void)hipFree(dy);
     if (e != hipSuccess) return mp_fail(MP_ERR_HIP, std::string("mp_unfold_simulate: ") + hipGetErrorString(e));
     return MP_OK;
 }
@@ -2296,18 +2249,17 @@ static int32_t importance_run(const mp_model_desc* model, const double* args0, c
     }
     if (resampled_indices && num_ret_samples > 0) {
         // importance_resampling: M categorical draws over exp(lnw) (importance.rs:44-47), slot j of DOM_IS
-        uint32_t* d_idx = nullptr;
-        HIPCK(hipMalloc(&d_idx, sizeof(uint32_t) * num_ret_samples));
+        mp_dev<uint32_t> d_idx;
+        HIPCK(mp_hipMalloc(d_idx, num_ret_samples));
         const int grid = (int)std::min<u64>((num_ret_samples + KG_THREADS * KG_ITEMS - 1) / (KG_THREADS * KG_ITEMS), (u64)K3_MAX_BLOCKS);
         hipLaunchKernelGGL(k_resample_gather<0>, dim3(grid), dim3(KG_THREADS), table_lds(h->nt, KG_THREADS), h->stream, h->n, (u64)num_ret_samples,
                            h->n_global, (u64)0, (uint32_t)MP_DOM_IS, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), 0u, h->S, h->ops->dim_state, h->cx,
-                           h->guide, h->tile_m, h->tile_W, h->tile_W2, h->nt, (const double*)nullptr, (double*)nullptr, d_idx, (double*)nullptr,
+                           h->guide, h->tile_m, h->tile_W, h->tile_W2, h->nt, (const double*)nullptr, (double*)nullptr, d_idx.get(), (double*)nullptr,
                            (mp_dev_scalars*)nullptr);
         rc = check_launch("k_resample_gather(IS)");
         std::vector<uint32_t> idx(num_ret_samples);
         hipError_t e1 = hipMemcpyAsync(idx.data(), d_idx, sizeof(uint32_t) * num_ret_samples, hipMemcpyDeviceToHost, h->stream);
         hipError_t e2 = hipStreamSynchronize(h->stream);
-        (void)hipFree(d_idx);
         if (rc != MP_OK) return rc;
         if (e1 != hipSuccess || e2 != hipSuccess) return mp_fail(MP_ERR_HIP, "importance_resampling: index copy failed");
         for (uint64_t j = 0; j < num_ret_samples; ++j) resampled_indices[j] = idx[j];
@@ -2349,15 +2301,14 @@ int32_t mp_is_finish_device(const double* d_logw, uint64_t n, uint64_t num_ret, 
     hipStream_t st = (hipStream_t)stream;
     const int S = 62 - ceil_log2_u64(n);
     struct Bufs {
-        mp_cx* cx = nullptr; unsigned short* guide = nullptr; u64* tiles = nullptr; mp_dev_scalars* scal = nullptr; double* tmp = nullptr; uint32_t* idx = nullptr;
-        ~Bufs() { (void)hipFree(cx); (void)hipFree(guide); (void)hipFree(tiles); (void)hipFree(scal); (void)hipFree(tmp); (void)hipFree(idx); }
+        mp_dev<mp_cx> cx; mp_dev<unsigned short> guide; mp_dev<u64> tiles; mp_dev<mp_dev_scalars> scal; mp_dev<double> tmp; mp_dev<uint32_t> idx;
     } b;
-    HIPCK(hipMalloc(&b.cx, sizeof(mp_cx) * (size_t)nt * TILE));
-    HIPCK(hipMalloc(&b.guide, sizeof(unsigned short) * (size_t)nt * GUIDE_N));
-    HIPCK(hipMalloc(&b.tiles, sizeof(u64) * 3 * (size_t)nt));
-    HIPCK(hipMalloc(&b.scal, sizeof(mp_dev_scalars)));
+    HIPCK(mp_hipMalloc(b.cx, (size_t)nt * TILE));
+    HIPCK(mp_hipMalloc(b.guide, (size_t)nt * GUIDE_N));
+    HIPCK(mp_hipMalloc(b.tiles, 3 * (size_t)nt));
+    HIPCK(mp_hipMalloc(b.scal, 1));
     HIPCK(hipMemsetAsync(b.scal, 0, sizeof(mp_dev_scalars), st));
-    double* tile_m = reinterpret_cast<double*>(b.tiles);
+    double* tile_m = reinterpret_cast<double*>(b.tiles.get());
     u64 *tile_W = b.tiles + nt, *tile_W2 = b.tiles + 2 * (size_t)nt;
     const size_t lds = table_lds(nt, K3_THREADS);
     if (lds > 48 * 1024) {
@@ -2377,7 +2328,7 @@ int32_t mp_is_finish_device(const double* d_logw, uint64_t n, uint64_t num_ret, 
     if (hs.degenerate) return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
     if (log_ml_estimate) *log_ml_estimate = hs.lml_fresh;
     if (log_normalized_weights) {
-        HIPCK(hipMalloc(&b.tmp, sizeof(double) * n));
+        HIPCK(mp_hipMalloc(b.tmp, n));
         hipLaunchKernelGGL(k_sub_scalar, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_logw, &b.scal->L, (u64)n, b.tmp);
         rc = check_launch("k_sub_scalar");
         if (rc != MP_OK) return rc;
@@ -2385,7 +2336,7 @@ int32_t mp_is_finish_device(const double* d_logw, uint64_t n, uint64_t num_ret, 
         HIPCK(hipStreamSynchronize(st));
     }
     if (resampled_indices && num_ret > 0) {
-        HIPCK(hipMalloc(&b.idx, sizeof(uint32_t) * num_ret));
+        HIPCK(mp_hipMalloc(b.idx, num_ret));
         const int grid = (int)std::min<u64>((num_ret + KG_THREADS * KG_ITEMS - 1) / (KG_THREADS * KG_ITEMS), (u64)K3_MAX_BLOCKS);
         hipLaunchKernelGGL(k_resample_gather<0>, dim3(grid), dim3(KG_THREADS), lds, st, (u64)n, (u64)num_ret, (u64)n, (u64)0, (uint32_t)MP_DOM_IS, (uint32_t)seed,
                            (uint32_t)(seed >> 32), 0u, S, 1, b.cx, b.guide, tile_m, tile_W, tile_W2, nt, (const double*)nullptr, (double*)nullptr, b.idx,

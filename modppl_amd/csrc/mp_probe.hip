@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mp_dists.h"
+#include "mp_hip_own.h"
 #include "mp_linalg.h"
 
 __global__ void k_probe_math(int op, const double* a, const double* b, const double* c, long long n, double* out) {
@@ -129,76 +130,65 @@ __global__ void k_probe_mfma_f64(const double* A, const double* B, const double*
 
 #define PCK(call)                                                              \
     do {                                                                       \
-        hipError_t e_ = (call);                                                \
-        if (e_ != hipSuccess) { rc = MP_ERR_HIP; goto done; }                  \
+        if ((call) != hipSuccess) return MP_ERR_HIP;                           \
     } while (0)
 
 extern "C" {
 
 int32_t mp_probe_math(int32_t op, const double* a, const double* b, const double* c, int64_t n, double* out, int32_t device) {
     if (op < MP_PROBE_EXP || op > MP_PROBE_ATAN2 || !a || !out || n < 1) return MP_ERR_INVALID_ARG;
-    int32_t rc = MP_OK;
-    double *da = nullptr, *db = nullptr, *dc = nullptr, *dout = nullptr;
+    mp_dev<double> da, db, dc, dout;
     const size_t bytes = sizeof(double) * (size_t)n;
     PCK(hipSetDevice(device));
-    PCK(hipMalloc(&da, bytes)); PCK(hipMalloc(&db, bytes)); PCK(hipMalloc(&dc, bytes)); PCK(hipMalloc(&dout, bytes));
+    PCK(mp_hipMalloc(da, bytes / sizeof(double))); PCK(mp_hipMalloc(db, bytes / sizeof(double))); PCK(mp_hipMalloc(dc, bytes / sizeof(double))); PCK(mp_hipMalloc(dout, bytes / sizeof(double)));
     PCK(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
     if (b) PCK(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice)); else PCK(hipMemset(db, 0, bytes));
     if (c) PCK(hipMemcpy(dc, c, bytes, hipMemcpyHostToDevice)); else PCK(hipMemset(dc, 0, bytes));
     hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, da, db, dc, (long long)n, dout);
     PCK(hipGetLastError());
     PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc); (void)hipFree(dout);
-    return rc;
+    return MP_OK;
 }
 
 int32_t mp_probe_normal_sample(uint64_t seed, uint32_t slot0, uint32_t step, uint32_t domain, uint32_t site, double mu, double sd,
                                int64_t n, double* out, int32_t device) {
-    int32_t rc = MP_OK;
-    double* dout = nullptr;
+    mp_dev<double> dout;
     const size_t bytes = sizeof(double) * (size_t)n;
     PCK(hipSetDevice(device));
-    PCK(hipMalloc(&dout, bytes));
+    PCK(mp_hipMalloc(dout, bytes / sizeof(double)));
     hipLaunchKernelGGL(k_probe_normal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), slot0, step,
                        domain, site, mu, sd, (long long)n, dout);
     PCK(hipGetLastError());
     PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(dout);
-    return rc;
+    return MP_OK;
 }
 
 int32_t mp_probe_u01(uint64_t seed, uint32_t slot0, uint32_t step, uint32_t domain, uint32_t site, uint32_t attempt, int64_t n,
                      double* out, int32_t device) {
-    int32_t rc = MP_OK;
-    double* dout = nullptr;
+    mp_dev<double> dout;
     const size_t bytes = sizeof(double) * 2 * (size_t)n;
     PCK(hipSetDevice(device));
-    PCK(hipMalloc(&dout, bytes));
+    PCK(mp_hipMalloc(dout, bytes / sizeof(double)));
     hipLaunchKernelGGL(k_probe_u01, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), slot0, step,
                        domain, site, attempt, (long long)n, dout);
     PCK(hipGetLastError());
     PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(dout);
-    return rc;
+    return MP_OK;
 }
 
 int32_t mp_probe_mvnormal(int32_t k, int32_t chain, const double* x, const double* mu, const double* cov, int64_t n, double* logpdf_out,
                           uint64_t seed, uint32_t slot0, uint32_t step, uint32_t domain, uint32_t site, double* sample_out, int32_t device) {
     if (k < 1 || k > MP_PROBE_MAX_K || !mu || !cov || n < 1) return MP_ERR_INVALID_ARG;
-    int32_t rc = MP_OK;
     const std::vector<double> c(cov, cov + (size_t)k * k);
     std::vector<double> inv, T;
     const double det = mp_host_det(c, k);
-    double *dx = nullptr, *dmu = nullptr, *dm = nullptr, *dout = nullptr;
+    mp_dev<double> dx, dmu, dm, dout;
     PCK(hipSetDevice(device));
-    PCK(hipMalloc(&dmu, sizeof(double) * k)); PCK(hipMalloc(&dm, sizeof(double) * k * k)); PCK(hipMalloc(&dout, sizeof(double) * (size_t)n * k));
+    PCK(mp_hipMalloc(dmu, k)); PCK(mp_hipMalloc(dm, (size_t)k * k)); PCK(mp_hipMalloc(dout, (size_t)n * k));
     PCK(hipMemcpy(dmu, mu, sizeof(double) * k, hipMemcpyHostToDevice));
     if (logpdf_out) {
-        if (!x || !mp_host_inverse(c, k, inv)) { rc = MP_ERR_INVALID_ARG; goto done; }   // try_inverse().unwrap() panics (mvnormal.rs:18)
-        PCK(hipMalloc(&dx, sizeof(double) * (size_t)n * k));
+        if (!x || !mp_host_inverse(c, k, inv)) return MP_ERR_INVALID_ARG;   // try_inverse().unwrap() panics (mvnormal.rs:18)
+        PCK(mp_hipMalloc(dx, (size_t)n * k));
         PCK(hipMemcpy(dx, x, sizeof(double) * (size_t)n * k, hipMemcpyHostToDevice));
         PCK(hipMemcpy(dm, inv.data(), sizeof(double) * k * k, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_probe_mvnormal_logpdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, k, chain, dx, dmu, dm, mp_log(det), (long long)n, dout);
@@ -213,9 +203,7 @@ int32_t mp_probe_mvnormal(int32_t k, int32_t chain, const double* x, const doubl
         PCK(hipGetLastError());
         PCK(hipMemcpy(sample_out, dout, sizeof(double) * (size_t)n * k, hipMemcpyDeviceToHost));
     }
-done:
-    (void)hipFree(dx); (void)hipFree(dmu); (void)hipFree(dm); (void)hipFree(dout);
-    return rc;
+    return MP_OK;
 }
 
 int32_t mp_probe_dist(int32_t dist, int32_t op, const double* x, const double* p0, const double* p1, int64_t n, uint64_t seed, uint32_t slot0,
@@ -223,37 +211,31 @@ int32_t mp_probe_dist(int32_t dist, int32_t op, const double* x, const double* p
     if (dist < 0 || dist > MP_PROBE_DIST_LOG1P || (op != 0 && op != 1) || (op == 0 && !x) || (op == 1 && dist > MP_PROBE_DIST_UNIFORM_DISCRETE) ||
         n < 1 || !out)
         return MP_ERR_INVALID_ARG;
-    int32_t rc = MP_OK;
-    double *dx = nullptr, *dp0 = nullptr, *dp1 = nullptr, *dout = nullptr;
+    mp_dev<double> dx, dp0, dp1, dout;
     const size_t bytes = sizeof(double) * (size_t)n;
     PCK(hipSetDevice(device));
-    PCK(hipMalloc(&dout, bytes));
-    if (op == 0) { PCK(hipMalloc(&dx, bytes)); PCK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice)); }
-    if (p0) { PCK(hipMalloc(&dp0, bytes)); PCK(hipMemcpy(dp0, p0, bytes, hipMemcpyHostToDevice)); }
-    if (p1) { PCK(hipMalloc(&dp1, bytes)); PCK(hipMemcpy(dp1, p1, bytes, hipMemcpyHostToDevice)); }
+    PCK(mp_hipMalloc(dout, bytes / sizeof(double)));
+    if (op == 0) { PCK(mp_hipMalloc(dx, bytes / sizeof(double))); PCK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice)); }
+    if (p0) { PCK(mp_hipMalloc(dp0, bytes / sizeof(double))); PCK(hipMemcpy(dp0, p0, bytes, hipMemcpyHostToDevice)); }
+    if (p1) { PCK(mp_hipMalloc(dp1, bytes / sizeof(double))); PCK(hipMemcpy(dp1, p1, bytes, hipMemcpyHostToDevice)); }
     hipLaunchKernelGGL(k_probe_dist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)dist, (int)op, dx, dp0, dp1, (long long)n,
                        (uint32_t)seed, (uint32_t)(seed >> 32), slot0, step, domain, site, dout);
     PCK(hipGetLastError());
     PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(dx); (void)hipFree(dp0); (void)hipFree(dp1); (void)hipFree(dout);
-    return rc;
+    return MP_OK;
 }
 
 int32_t mp_probe_mfma_f64(const double* A16x4, const double* B4x16, const double* C16x16, double* D16x16, int32_t device) {
-    int32_t rc = MP_OK;
-    double *da = nullptr, *db = nullptr, *dc = nullptr, *dd = nullptr;
+    mp_dev<double> da, db, dc, dd;
     PCK(hipSetDevice(device));
-    PCK(hipMalloc(&da, sizeof(double) * 64)); PCK(hipMalloc(&db, sizeof(double) * 64)); PCK(hipMalloc(&dc, sizeof(double) * 256)); PCK(hipMalloc(&dd, sizeof(double) * 256));
+    PCK(mp_hipMalloc(da, 64)); PCK(mp_hipMalloc(db, 64)); PCK(mp_hipMalloc(dc, 256)); PCK(mp_hipMalloc(dd, 256));
     PCK(hipMemcpy(da, A16x4, sizeof(double) * 64, hipMemcpyHostToDevice));
     PCK(hipMemcpy(db, B4x16, sizeof(double) * 64, hipMemcpyHostToDevice));
     PCK(hipMemcpy(dc, C16x16, sizeof(double) * 256, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_probe_mfma_f64, dim3(1), dim3(64), 0, 0, da, db, dc, dd);
     PCK(hipGetLastError());
     PCK(hipMemcpy(D16x16, dd, sizeof(double) * 256, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc); (void)hipFree(dd);
-    return rc;
+    return MP_OK;
 }
 
 }  // extern "C"

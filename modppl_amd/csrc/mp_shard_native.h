@@ -14,13 +14,13 @@ struct mp_shard_native_state {
     int world = 0;
     bool fixed = true, cap_forced = false;
     uint64_t cap = 0, fixed_max_bytes = 4ull << 20;
-    uint64_t* tiles = nullptr;       // [3][nt] packed level-0 tiles of this shard
-    uint64_t* tiles_all = nullptr;   // [world][3][nt]
-    double* send = nullptr;     // equal splits: [world][cap][d + 1]
-    double* rows[2] = {nullptr, nullptr};   // [world * cap + n][d + 1], used alternately (the previous one is still read by the step in flight)
+    mp_dev<uint64_t> tiles;       // [3][nt] packed level-0 tiles of this shard
+    mp_dev<uint64_t> tiles_all;   // [world][3][nt]
+    mp_dev<double> send;        // equal splits: [world][cap][d + 1]
+    mp_dev<double> rows[2];     // [world * cap + n][d + 1], used alternately (the previous one is still read by the step in flight)
     int flip = 0;
-    double* xsend[2] = {nullptr, nullptr};  // exact sizes: grow-only, two sets used alternately
-    double* xrows[2] = {nullptr, nullptr};
+    mp_dev<double> xsend[2];    // exact sizes: grow-only, two sets used alternately
+    mp_dev<double> xrows[2];
     uint64_t xsend_rows[2] = {0, 0}, xrows_rows[2] = {0, 0};
     int xflip = 0;
     uint64_t fallbacks = 0, last_exchange_rows = 0;
@@ -28,23 +28,18 @@ struct mp_shard_native_state {
     bool have_counts = false;
 };
 
-static void shard_native_free(mp_shard_native_state* s) {
-    if (!s) return;
-    (void)hipFree(s->tiles); (void)hipFree(s->tiles_all); (void)hipFree(s->send);
-    for (int k = 0; k < 2; ++k) { (void)hipFree(s->rows[k]); (void)hipFree(s->xsend[k]); (void)hipFree(s->xrows[k]); }
-    delete s;
-}
+void mp_shard_native_delete::operator()(mp_shard_native_state* s) const { delete s; }
 
 static int32_t shard_native_alloc_fixed(mp_pf* h, mp_shard_native_state* s, uint64_t cap) {
     const int d = h->ops->dim_state;
-    (void)hipFree(s->send); (void)hipFree(s->rows[0]); (void)hipFree(s->rows[1]);
-    s->send = nullptr; s->rows[0] = s->rows[1] = nullptr;
+    s->send.reset(); s->rows[0].reset(); s->rows[1].reset();   // (all three before the first of the larger ones is allocated)
     s->cap = cap;
-    const size_t send_b = sizeof(double) * (size_t)s->world * cap * (d + 1), rows_b = sizeof(double) * ((size_t)s->world * cap + h->n) * (d + 1);
-    HIPCK(hipMalloc(&s->send, send_b));
+    const size_t send_n = (size_t)s->world * cap * (d + 1), rows_n = ((size_t)s->world * cap + h->n) * (d + 1);
+    const size_t send_b = sizeof(double) * send_n, rows_b = sizeof(double) * rows_n;
+    HIPCK(mp_hipMalloc(s->send, send_n));
     HIPCK(hipMemsetAsync(s->send, 0, send_b, h->stream));
     for (int k = 0; k < 2; ++k) {
-        HIPCK(hipMalloc(&s->rows[k], rows_b));
+        HIPCK(mp_hipMalloc(s->rows[k], rows_n));
         HIPCK(hipMemsetAsync(s->rows[k], 0, rows_b, h->stream));
     }
     s->flip = 0;
@@ -52,12 +47,12 @@ static int32_t shard_native_alloc_fixed(mp_pf* h, mp_shard_native_state* s, uint
 }
 
 static int32_t shard_native_init(mp_pf* h, int world) {
-    auto* s = new mp_shard_native_state();
-    h->native = s;
+    h->native.reset(new mp_shard_native_state());
+    mp_shard_native_state* s = h->native.get();
     s->world = world;
     const int d = h->ops->dim_state;
-    HIPCK(hipMalloc(&s->tiles, sizeof(uint64_t) * 3 * h->nt));
-    HIPCK(hipMalloc(&s->tiles_all, sizeof(uint64_t) * 3 * h->nt * (size_t)world));
+    HIPCK(mp_hipMalloc(s->tiles, 3 * h->nt));
+    HIPCK(mp_hipMalloc(s->tiles_all, 3 * h->nt * (size_t)world));
     int32_t rc = mp_pf_shard_bind_tiles(h, s->tiles);   // the filter keeps its tiles where the all-gather reads them
     if (rc != MP_OK) return rc;
     // surplus rows per pair of ranks in the equal-split exchange: the surplus of a rank is the spread of a Binomial(N, ~1/world)
@@ -81,12 +76,10 @@ static int32_t shard_native_init(mp_pf* h, int world) {
     return MP_OK;
 }
 
-static int32_t shard_native_grow(double** buf, uint64_t* have_rows, uint64_t want_rows, int width) {
-    if (*buf && *have_rows >= want_rows) return MP_OK;
-    (void)hipFree(*buf);
-    *buf = nullptr;
+static int32_t shard_native_grow(mp_dev<double>& buf, uint64_t* have_rows, uint64_t want_rows, int width) {
+    if (buf && *have_rows >= want_rows) return MP_OK;
     const uint64_t rows = want_rows + want_rows / 4 + 64;
-    HIPCK(hipMalloc(buf, sizeof(double) * rows * (size_t)width));
+    HIPCK(mp_hipMalloc(buf, rows * (size_t)width));
     *have_rows = rows;
     return MP_OK;
 }
@@ -118,12 +111,11 @@ int32_t mp_pf_shard_resample(mp_pf* h, const mp_transport* t, int32_t world, int
     if (!solo && (!t || !t->all_gather || !t->all_to_all)) return mp_fail(MP_ERR_INVALID_ARG, "a world of more than one needs a transport");
     HIPCK(hipSetDevice(h->device));
     if (!h->native || h->native->world != world) {
-        shard_native_free(h->native);
-        h->native = nullptr;
+        h->native.reset();
         int32_t rci = shard_native_init(h, world);
         if (rci != MP_OK) return rci;
     }
-    mp_shard_native_state* s = h->native;
+    mp_shard_native_state* s = h->native.get();
     const int d = h->ops->dim_state;
     const size_t row_b = sizeof(double) * (size_t)(d + 1);
     int32_t rc = mp_pf_shard_tiles_packed(h, s->tiles);
@@ -185,9 +177,9 @@ int32_t mp_pf_shard_resample(mp_pf* h, const mp_transport* t, int32_t world, int
     const uint64_t keep_rows = d == 1 ? h->n : 0;
     const int k = s->xflip;
     s->xflip ^= 1;
-    rc = shard_native_grow(&s->xsend[k], &s->xsend_rows[k], std::max<uint64_t>(n_send, 1), d + 1);
+    rc = shard_native_grow(s->xsend[k], &s->xsend_rows[k], std::max<uint64_t>(n_send, 1), d + 1);
     if (rc != MP_OK) return rc;
-    rc = shard_native_grow(&s->xrows[k], &s->xrows_rows[k], std::max<uint64_t>(n_recv + keep_rows, 1), d + 1);
+    rc = shard_native_grow(s->xrows[k], &s->xrows_rows[k], std::max<uint64_t>(n_recv + keep_rows, 1), d + 1);
     if (rc != MP_OK) return rc;
     rc = mp_pf_shard_owned_expand(h, world, rank, 0, s->xsend[k], s->xrows[k], n_recv);
     if (rc != MP_OK) return rc;
@@ -232,12 +224,11 @@ int32_t mp_pf_shard_query_native(mp_pf* h, const mp_transport* t, int32_t world,
     if (!solo && (!t || !t->all_gather)) return mp_fail(MP_ERR_INVALID_ARG, "a world of more than one needs a transport");
     HIPCK(hipSetDevice(h->device));
     if (!h->native || h->native->world != world) {
-        shard_native_free(h->native);
-        h->native = nullptr;
+        h->native.reset();
         int32_t rci = shard_native_init(h, world);
         if (rci != MP_OK) return rci;
     }
-    mp_shard_native_state* s = h->native;
+    mp_shard_native_state* s = h->native.get();
     int32_t rc = mp_pf_shard_tiles_packed(h, s->tiles);
     if (rc != MP_OK) return rc;
     const uint64_t* tiles_all = s->tiles;
