@@ -79,9 +79,11 @@ inline bool mp_host_cholesky(const std::vector<double>& m, int n, std::vector<do
 // eigenvectors * diag(sqrt(eigenvalues)).  nalgebra's symmetric_eigen is an un-vendored dependency; its result is defined only
 // up to the order and sign of the eigenvectors, which `transform * z` depends on, so the build fixes one: cyclic Jacobi
 // rotations (upper-triangle sweep order, at most 64 sweeps), eigenpairs in the order the diagonal ends up in.  A negative
-// eigenvalue gives NaN columns, as `.sqrt()` does in the reference — except round-off: an eigenvalue in [-64 eps lambda_max, 0)
-// (what a zero eigenvalue of a singular covariance comes out as) is taken as zero, where the reference's result depends on
-// the last bit of nalgebra's iteration.
+// eigenvalue gives NaN columns, as `.sqrt()` does in the reference — except round-off: an eigenvalue within 64 eps lambda_max
+// of zero, on either side (what a zero eigenvalue of a singular covariance comes out as), is taken as zero, where the
+// reference's result depends on the last bit of nalgebra's iteration.  (Both sides: the square root of a round-off eigenvalue
+// of +1e-16 lambda_max is 1e-8 sqrt(lambda_max), noise in a direction the covariance gives none;
+// tests/test_model_laws.py holds the null-space component of a step's residual to round-off.)
 inline void mp_host_sym_eigen_transform(std::vector<double> a, int n, std::vector<double>& T) {
     std::vector<double> v((size_t)n * n, 0.);
     for (int i = 0; i < n; ++i) v[i * n + i] = 1.;
@@ -119,7 +121,7 @@ inline void mp_host_sym_eigen_transform(std::vector<double> a, int n, std::vecto
     T.assign((size_t)n * n, 0.);
     for (int j = 0; j < n; ++j) {
         double lam = a[j * n + j];
-        if (lam < 0. && lam >= -64. * 2.220446049250313e-16 * lmax) lam = 0.;
+        if (std::fabs(lam) <= 64. * 2.220446049250313e-16 * lmax) lam = 0.;
         const double sq = std::sqrt(lam);
         for (int i = 0; i < n; ++i) T[i * n + j] = v[i * n + j] * sq;
     }

@@ -213,7 +213,7 @@ inline Mat symmetric_eigen_transform(Mat a) {
     Mat T(n, std::vector<double>((size_t)n * n, 0.));
     for (int j = 0; j < n; ++j) {
         double lam = a(j, j);
-        if (lam < 0. && lam >= -64. * 2.220446049250313e-16 * lmax) lam = 0.;   // round-off of a zero eigenvalue
+        if (std::fabs(lam) <= 64. * 2.220446049250313e-16 * lmax) lam = 0.;   // round-off of a zero eigenvalue, either sign
         const double sq = std::sqrt(lam);
         for (int i = 0; i < n; ++i) T(i, j) = v(i, j) * sq;
     }
