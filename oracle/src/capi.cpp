@@ -509,6 +509,8 @@ struct oracle_mhfn {
     std::vector<MhFnTrace> traces;
     uint64_t seed = 0, iters = 0;
     bool canonical = false;
+    std::vector<int32_t> data_sites;   // the creating call's constraints on declared data sites (ids >= ns): a later generate with a
+    std::vector<double> data_vals;     // per-chain table of the model's own slots cannot name them, and observes them again
 };
 int32_t oracle_mhfn_create(int32_t kind, const double* params, int32_t n_params, const int32_t* cons_sites, const double* cons_vals, int32_t n_cons,
                            uint64_t n_chains, uint64_t seed, int32_t canon, oracle_mhfn** out) {
@@ -519,6 +521,8 @@ int32_t oracle_mhfn_create(int32_t kind, const double* params, int32_t n_params,
         h->seed = seed; h->canonical = canon != 0;
         oracle_pf::Scope scope(h->canonical);
         h->m = it->second(params, n_params);
+        for (int q = 0; q < n_cons; ++q)
+            if (cons_sites[q] >= h->m->ns()) { h->data_sites.push_back(cons_sites[q]); h->data_vals.push_back(cons_vals[q]); }
         for (uint64_t i = 0; i < n_chains; ++i) {
             Rng r; r.seed = seed; r.slot = (uint32_t)i; r.step = 0;
             h->traces.push_back(h->m->model().generate(r, 0, h->m->constraints(cons_sites, cons_vals, n_cons)).first);
@@ -565,11 +569,12 @@ int32_t oracle_mhfn_regen(oracle_mhfn* h, const int32_t* mask_sites, int32_t n_m
 }
 // ---- the GFI operations one at a time (gfi.rs:57-90), chain by chain through the dynamic machinery: the checker of mp_fn_* ----
 static DynTrie mhfn_chain_constraints(oracle_mhfn* h, const int32_t* sites, const double* vals, int32_t n_cons, const double* chain_values,
-                                      const uint64_t* chain_present, size_t i) {
+                                      const uint64_t* chain_present, size_t i, bool with_data = false) {
     if (!chain_values) return h->m->constraints(sites, vals, n_cons);
     const int ns = h->m->ns();
     std::vector<int32_t> s2;
     std::vector<double> v2;
+    if (with_data) { s2 = h->data_sites; v2 = h->data_vals; }   // generate: the observations stay observed, as on the device (bound arrays)
     for (int k = 0; k < ns; ++k)
         if ((chain_present[i] >> k) & 1u) { s2.push_back(k); v2.push_back(chain_values[i * (size_t)ns + k]); }
     return h->m->constraints(s2.data(), v2.data(), (int)s2.size());
@@ -645,7 +650,7 @@ int32_t oracle_mhfn_generate(oracle_mhfn* h, uint32_t rng_step, const int32_t* s
         const uint32_t step = mhfn_step(h, rng_step);
         for (size_t i = 0; i < h->traces.size(); ++i) {
             Rng r; r.seed = h->seed; r.slot = (uint32_t)i; r.step = step;
-            auto [tr, w] = h->m->model().generate(r, 0, mhfn_chain_constraints(h, sites, vals, n_cons, chain_values, chain_present, i));
+            auto [tr, w] = h->m->model().generate(r, 0, mhfn_chain_constraints(h, sites, vals, n_cons, chain_values, chain_present, i, true));
             h->traces[i] = std::move(tr);
             if (weights) weights[i] = w;
         }
@@ -719,6 +724,16 @@ int32_t oracle_mhfn_static_update(oracle_mhfn_static* h, const int32_t* sites, c
 int32_t oracle_mhfn_static_read(oracle_mhfn_static* h, double* values, uint64_t* present, uint64_t* panics) {
     GUARD({ h->r->read(values, present); if (panics) *panics = h->r->panics(); })
 }
+// what the law tests (tests/mh_laws.py) need of the static handlers beyond moves: per-chain constraints, logjp, a proposal's choices
+int32_t oracle_mhfn_static_plant(oracle_mhfn_static* h, const double* chain_values, const uint64_t* chain_present, uint32_t step, double* weights) {
+    GUARD({ h->r->plant(chain_values, chain_present, step, weights); })
+}
+int32_t oracle_mhfn_static_logjp(oracle_mhfn_static* h, double* out) { GUARD({ h->r->logjp(out); }) }
+int32_t oracle_mhfn_static_propose(oracle_mhfn_static* h, int32_t proposal_kind, const double* args, int32_t n_args, uint32_t step, double* choice_values,
+                                   uint64_t* choice_present, double* weights) {
+    GUARD({ h->r->propose(proposal_kind, args, n_args, step, choice_values, choice_present, weights); })
+}
+int32_t oracle_mhfn_static_n_sites(oracle_mhfn_static* h, int32_t* out) { GUARD({ *out = h->r->ns(); }) }
 int32_t oracle_mhfn_static_destroy(oracle_mhfn_static* h) { delete h; return MP_OK; }
 
 // ---- mh.rs over N independent chains of hierarchical_model ------------------------------------

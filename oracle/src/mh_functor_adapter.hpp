@@ -259,6 +259,11 @@ struct MhFnStatic {
     virtual uint64_t panics() const = 0;
     // mp_fn_update's per-lane work (k_fn_update) with constraints shared by all chains: weights and discard presence out
     virtual void update(const int32_t* sites, const double* vals, int n_cons, int unknown, uint32_t step, double* weights, uint64_t* disc_present) = 0;
+    // for the law tests (tests/mh_laws.py): k_fn_generate with one row of constraints per chain ([n][ns] values, one presence word each),
+    // k_fn_logjp and k_fn_propose per lane
+    virtual void plant(const double* vals, const uint64_t* present, uint32_t step, double* weights) = 0;
+    virtual void logjp(double* out) const = 0;
+    virtual void propose(int kind, const double* args, int n_args, uint32_t step, double* cvals, uint64_t* cpresent, double* weights) const = 0;
 };
 template <class M>
 struct MhFnStaticT;
@@ -267,6 +272,13 @@ using MhFnStaticProposal = std::function<uint64_t(MhFnStaticT<M>&, const double*
 template <class M>
 std::map<int, MhFnStaticProposal<M>>& mhfn_static_proposals() {
     static std::map<int, MhFnStaticProposal<M>> r;
+    return r;
+}
+template <class M>
+using MhFnStaticProposer = std::function<void(const MhFnStaticT<M>&, const double*, int, uint32_t, double*, uint64_t*, double*)>;
+template <class M>
+std::map<int, MhFnStaticProposer<M>>& mhfn_static_proposers() {
+    static std::map<int, MhFnStaticProposer<M>> r;
     return r;
 }
 template <class M>
@@ -387,6 +399,51 @@ struct MhFnStaticT : MhFnStatic {
             for (int k = 0; k < M::NS; ++k) vals[i * (size_t)M::NS + k] = tr[i].has(k) ? tr[i].val[k] : 0.;
         }
     }
+    static mp_fn_trace<M::NS> row(const double* vals, uint64_t present) {
+        mp_fn_trace<M::NS> c;
+        mp_fn_clear(c);
+        c.present = (mp_fn_bits_t<M::NS>)present;
+        for (int k = 0; k < M::NS; ++k) c.val[k] = c.has(k) ? vals[k] : 0.;
+        return c;
+    }
+    void plant(const double* vals, const uint64_t* present, uint32_t step, double* weights) override {   // k_fn_generate
+        for (size_t i = 0; i < tr.size(); ++i) {
+            const mp_fn_trace<M::NS> c = row(vals + i * (size_t)M::NS, present[i]);
+            const mp_stream s = stream(i, step);
+            mp_fn_handler<M::NS, MP_FN_GENERATE, M> g(s, MP_DOM_MODEL, nullptr, &c);
+            model(g);
+            g.finish();
+            n_panic += g.panic;
+            if (!g.panic) tr[i] = g.tr;
+            weights[i] = g.weight;
+        }
+    }
+    void logjp(double* out) const override {   // k_fn_logjp: the stored values scored again, every choice constrained
+        for (size_t i = 0; i < tr.size(); ++i) {
+            mp_fn_trace<M::NS> c = tr[i];
+            for (int k = 0; k < M::NS; ++k) { c.lp[k] = 0.; c.subw[k] = 0.; if (!c.has(k)) c.val[k] = 0.; }
+            const mp_stream s = stream(0, 0);
+            mp_fn_handler<M::NS, MP_FN_GENERATE, M> g(s, MP_DOM_MODEL, nullptr, &c);
+            model(g);
+            out[i] = mp_fn_has_data<M>::value ? mp_fn_logjp(g.tr) + g.dlp : mp_fn_logjp(g.tr);
+        }
+    }
+    template <class P>
+    void propose_with(const P& proposal, uint32_t step, double* cvals, uint64_t* cpresent, double* weights) const {   // k_fn_propose
+        for (size_t i = 0; i < tr.size(); ++i) {
+            const mp_stream s = stream(i, step);
+            mp_fn_handler<M::NS, MP_FN_SIMULATE, M> p(s, MP_DOM_PROPOSAL, nullptr, nullptr);
+            proposal(p, tr[i]);
+            weights[i] = p.weight;
+            cpresent[i] = p.tr.present;
+            for (int k = 0; k < M::NS; ++k) cvals[i * (size_t)M::NS + k] = p.tr.has(k) ? p.tr.val[k] : 0.;
+        }
+    }
+    void propose(int kind, const double* args, int n_args, uint32_t step, double* cvals, uint64_t* cpresent, double* weights) const override {
+        auto it = mhfn_static_proposers<M>().find(kind);
+        if (it == mhfn_static_proposers<M>().end()) throw Panic("no proposal of this kind is registered for the model");
+        it->second(*this, args, n_args, step, cvals, cpresent, weights);
+    }
 };
 using MhFnStaticFactory = std::function<std::shared_ptr<MhFnStatic>(const double*, int)>;
 inline std::map<int, MhFnStaticFactory>& mhfn_static_models() {
@@ -433,6 +490,12 @@ int mhfn_register_proposal(int kind, bool (*parse)(const double*, int, P&, std::
         std::string err;
         if (!parse(args, n_args, p, err)) throw Panic(err);
         return r.mh_with(p, n_iters);
+    };
+    mhfn_static_proposers<M>()[kind] = [parse](const MhFnStaticT<M>& r, const double* args, int n_args, uint32_t step, double* cv, uint64_t* cp, double* w) {
+        P p{};
+        std::string err;
+        if (!parse(args, n_args, p, err)) throw Panic(err);
+        r.propose_with(p, step, cv, cp, w);
     };
     return kind;
 }

@@ -662,7 +662,36 @@ class HostStaticFunctionChains:
                                                   C.c_uint32(rng_step), dptr(w), dp_.ctypes.data_as(C.POINTER(C.c_uint64))))
         return w, dp_
 
-    def trace(self, num_sites):
+    # ---- what tests/mh_laws.py needs beyond moves (k_fn_generate with per-chain constraints, k_fn_logjp, k_fn_propose per lane) ----
+    def _ns(self):
+        ns = C.c_int32()
+        self._ck(self.L.oracle_mhfn_static_n_sites(self.h, C.byref(ns)))
+        return ns.value
+
+    def generate(self, constraints, rng_step):
+        """per-chain constraints (values [n, num_sites], present [n]) only; the chains' traces are replaced; -> weights"""
+        ns = self._ns()
+        cv = np.ascontiguousarray(constraints[0], dtype=np.float64).reshape(self.n, ns)
+        cp = np.ascontiguousarray(constraints[1], dtype=np.uint64).reshape(self.n)
+        w = np.empty(self.n)
+        self._ck(self.L.oracle_mhfn_static_plant(self.h, dptr(cv), cp.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_uint32(rng_step), dptr(w)))
+        return w
+
+    def logjp(self):
+        out = np.empty(self.n)
+        self._ck(self.L.oracle_mhfn_static_logjp(self.h, dptr(out)))
+        return out
+
+    def propose(self, proposal_kind, proposal_args=(), rng_step=0):
+        ns = self._ns()
+        a = np.ascontiguousarray(proposal_args, dtype=np.float64).ravel()
+        cv, cp, w = np.zeros((self.n, ns)), np.zeros(self.n, dtype=np.uint64), np.empty(self.n)
+        self._ck(self.L.oracle_mhfn_static_propose(self.h, int(proposal_kind), dptr(a), int(a.size), C.c_uint32(rng_step), dptr(cv),
+                                                   cp.ctypes.data_as(C.POINTER(C.c_uint64)), dptr(w)))
+        return (cv, cp), w
+
+    def trace(self, num_sites=None):
+        num_sites = self._ns() if num_sites is None else num_sites
         vals = np.empty((self.n, num_sites))
         present = np.empty(self.n, dtype=np.uint64)
         pan = C.c_uint64()
