@@ -134,6 +134,15 @@ int32_t mp_pf_read_state(mp_pf* h, double* x_out);
 int32_t mp_pf_read_log_weights(mp_pf* h, double* out);
 /* parents (:20) of the most recent resample -> out[n_local] (global slot ids). */
 int32_t mp_pf_read_parents(mp_pf* h, uint32_t* out);
+/* Weighted mean and covariance of the cloud, reduced ON THE DEVICE: replaces the host-side reduction a caller of the reference writes over
+ * its public `traces` / `log_weights` fields (particle_filter.rs:13-20), i.e. mp_pf_read_state + mp_pf_read_log_weights and a loop over
+ * n particles.  A few dozen doubles cross the link instead of n * (dim_state + 1).  With m = max lw, a_i = exp(lw_i - m) (0 for -inf):
+ *   mean_out[j] = sum_i a_i x_ij / sum_i a_i;   cov_out[j][k] = sum_i a_i (x_ij - mean_j)(x_ik - mean_k) / sum_i a_i   (population form,
+ * no Bessel factor; row-major [d][d], exactly symmetric; NULL = mean only).  Every sum is the pairwise tree over GLOBAL slot ids of
+ * the result is a pure function of the stored values, the same bits on any launch geometry.  Synchronous, on the
+ * handle's stream; brings the handle to a readable state exactly as the two reads above do and changes nothing the filter computes
+ * afterwards.  All log-weights -inf: MP_ERR_DEGENERATE.  One shard of a larger world (n_global != n_particles): MP_ERR_UNSUPPORTED. */
+int32_t mp_pf_moments(mp_pf* h, double* mean_out, double* cov_out);
 /* traces[i].retv (Vec<State>) rebuilt from the recorded ancestry -> out[t_steps][dim_state].
  * Needs MP_PF_RECORD_HISTORY. */
 int32_t mp_pf_read_trajectory(mp_pf* h, uint64_t i, double* out, int32_t* t_steps);
@@ -417,6 +426,14 @@ int32_t mp_mh_n_sites(mp_mh* h, int32_t* out);
  * empty mask as above), mp_mh_read_logjp, mp_mh_iterations and mp_mh_destroy apply to these handles; mp_mh_read_state and
  * mp_mh_read_observations do not. */
 int32_t mp_mh_read_trace(mp_mh* h, double* values, uint32_t* present);
+/* Per-site count, mean and variance over the chains, reduced ON THE DEVICE: replaces the host-side reduction over mp_mh_read_trace's
+ * n_chains * n_sites doubles (what the reference's tests do with the traces they collect, tests/mh.rs; the filter's counterpart is the
+ * reduction over `traces` / `log_weights`, particle_filter.rs:13-20).  For site s (each slot of a vector-valued site is a site of its own),
+ * over the chains whose trace holds it: count_out[s]; mean_out[s]; var_out[s] = mean of (v - mean)^2 (population form; NULL = none).
+ * An absent chain contributes +0.0 whatever its stored value; a site no chain holds gives count 0 and NaN moments (not an error).  The sums
+ * are the pairwise tree over chain ids of DESIGN.md section 4.  All arrays [n_sites] (mp_mh_n_sites); the sub-calls' running weights are not
+ * summarised.  Hand-written chains (mp_mh_create, mp_mh_create_pointed): MP_ERR_UNSUPPORTED, as for mp_mh_read_trace. */
+int32_t mp_mh_site_moments(mp_mh* h, uint64_t* count_out, double* mean_out, double* var_out);
 
 /* ---- The GFI operations ONE AT A TIME, batched over the chains of a registered generative function ---------------------------
  * `GenFn::update / regenerate / propose / assess` are public in the reference (modppl/src/gfi.rs:57-90) and its tests call them

@@ -86,6 +86,15 @@ public:
         check(mp_pf_read_state(h_, x.data()));
         return x;
     }
+    // weighted mean [dim_state] and population covariance [dim_state][dim_state] (row-major) of the cloud, reduced on the device:
+    // the host-side reduction over states() and log_weights(), without moving the particles (mp_pf_moments)
+    struct Moments { std::vector<double> mean, cov; };
+    Moments moments(bool cov = true) {
+        const size_t d = (size_t)model_.dim_state;
+        Moments m{std::vector<double>(d), std::vector<double>(cov ? d * d : 0)};
+        check(mp_pf_moments(h_, m.mean.data(), cov ? m.cov.data() : nullptr));
+        return m;
+    }
     std::vector<double> log_weights() {
         std::vector<double> w(n_);
         check(mp_pf_read_log_weights(h_, w.data()));
@@ -219,6 +228,14 @@ public:
         values.resize(n_ * (size_t)ns_);
         present.resize(n_ * words());
         check(mp_mh_read_trace(h_, values.data(), present.data()));
+    }
+    // per site, over the chains whose trace holds it: count, mean and population variance, reduced on the device (mp_mh_site_moments);
+    // a site no chain holds: count 0, NaN moments
+    struct SiteMoments { std::vector<uint64_t> count; std::vector<double> mean, var; };
+    SiteMoments site_moments(bool var = true) {
+        SiteMoments m{std::vector<uint64_t>((size_t)ns_), std::vector<double>((size_t)ns_), std::vector<double>(var ? (size_t)ns_ : 0)};
+        check(mp_mh_site_moments(h_, m.count.data(), m.mean.data(), var ? m.var.data() : nullptr));
+        return m;
     }
     // ---- GenFn::update / regenerate / assess / propose one at a time, every chain per call (gfi.rs:57-90; mp_fn_* of the C ABI) ----
     // A per-chain table of choices: values[chain][site], present[chain][words()] — what propose() and update()'s discard return.

@@ -405,9 +405,14 @@ struct mp_mh {           // (every device pointer is a holder, mp_hip_own.h; the
     mp_dev<uint32_t> gfi_present;    // [n]
     mp_dev<double> gfi_cons;         // [n_sites][n]: per-chain constraint values
     mp_dev<uint32_t> gfi_cpresent;   // [n]: per-chain constraint presence
+    // mp_mh_site_moments (mp_moments.h), allocated on first use: partials of one pass ([columns][workgroups], two levels), the closed trees
+    mp_dev<double> mom_buf[2];
+    mp_dev<double> mom_res;          // {sum, count}[n_sites], mean[n_sites], centred sum of squares[n_sites]
     mp_dev<double> d_data;           // models with declared data sites (mp_genfn.h): [2][n_obs] = the covariates (params), the observed values
 };
 #include "mp_mh_fn.h"
+#define MP_MOMENTS_MH
+#include "mp_moments.h"   // mp_mh_site_moments: the tree reduction and its kernels (after every existing kernel)
 
 // acceptance count (and, for registered functions, the count of chains that reached a state the reference panics on)
 static int32_t mh_finish(mp_mh* h, uint64_t* accepted) {
@@ -718,6 +723,43 @@ int32_t mp_mh_read_trace(mp_mh* h, double* values, uint32_t* present) {
     { const int32_t rcp = present_to_host(h, h->fpresent, present); if (rcp != MP_OK) return rcp; }   // (waits for the stream)
     for (u64 i = 0; i < h->n; ++i)
         for (int k = 0; k < ns; ++k) values[i * (u64)ns + k] = v[(size_t)k * h->n + i];
+    return MP_OK;
+}
+
+// Per-site count, mean and variance over the chains, reduced on the device: replaces the host-side reduction over what a caller of the
+// reference collects from its public traces (particle_filter.rs:13-20 is the filter's side of the same gap; here mp_mh_read_trace and
+// a loop over chains).  Definition (the tree sum, presence SELECTS the value): mp_moments.h, DESIGN.md section 4.
+int32_t mp_mh_site_moments(mp_mh* h, uint64_t* count_out, double* mean_out, double* var_out) {
+    if (!h || !count_out || !mean_out) return mp_set_error(MP_ERR_INVALID_ARG, "null argument");
+    if (!h->fn) return mp_set_error(MP_ERR_UNSUPPORTED, "chains of a registered generative function only (mp_mh_create_fn)");
+    MHCK(hipSetDevice(h->device));
+    const int ns = h->fn->ns();
+    const u64 nb = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);
+    if (!h->mom_res) {
+        MHCK(mp_hipMalloc(h->mom_buf[0], 2 * (size_t)ns * nb));
+        MHCK(mp_hipMalloc(h->mom_buf[1], 2 * (size_t)ns * ((nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN)));
+        MHCK(mp_hipMalloc(h->mom_res, 4 * (size_t)ns));
+    }
+    double* const buf[2] = {h->mom_buf[0].get(), h->mom_buf[1].get()};
+    double* res = h->mom_res;
+    hipLaunchKernelGGL(k_mom_site1, dim3((unsigned)nb, (unsigned)ns), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->fvals, (const uint32_t*)h->fpresent, buf[0]);
+    mom_close<mom_add>(h->stream, buf, nb, 2u * (unsigned)ns, res);
+    if (var_out) {
+        hipLaunchKernelGGL(k_mom_site2, dim3((unsigned)nb, (unsigned)ns), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->fvals, (const uint32_t*)h->fpresent,
+                           (const double*)res, res + 2 * ns, buf[0]);
+        mom_close<mom_add>(h->stream, buf, nb, (unsigned)ns, res + 3 * ns);
+    }
+    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return mp_set_error(MP_ERR_HIP, std::string("mp_mh_site_moments kernels: ") + hipGetErrorString(e)); }
+    std::vector<double> r(4 * (size_t)ns);
+    MHCK(hipMemcpyAsync(r.data(), res, sizeof(double) * r.size(), hipMemcpyDeviceToHost, h->stream));
+    MHCK(hipStreamSynchronize(h->stream));
+    for (int s = 0; s < ns; ++s) {
+        const double cnt = r[2 * s + 1];   // a tree of 0.0 / 1.0: exact
+        count_out[s] = (uint64_t)cnt;
+        // without a variance pass nobody has formed the means on the device: the same IEEE division here (0 / 0 = NaN: a site nobody has)
+        mean_out[s] = var_out ? r[2 * ns + s] : r[2 * s] / cnt;
+        if (var_out) var_out[s] = r[3 * ns + s] / cnt;
+    }
     return MP_OK;
 }
 

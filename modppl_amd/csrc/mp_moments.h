@@ -1,0 +1,238 @@
+// mp_moments.h — on-device weighted moments of a particle cloud and of the chains of a registered function (gfx950, wave64).
+//
+// ONE definition ("Moments"), restated in numpy by tests/moments_ref.py and compared bit for bit:
+//
+//   TREE(v[0..n)):  pad v with +0.0 up to the next power of two; repeat v <- v[0::2] + v[1::2] until one element is left.
+//                   IEEE fp64, no contraction (-ffp-contract=off), indices are GLOBAL slot / chain ids.
+//
+// a + b == b + a and x + (+0.0) == x (up to the sign of a zero), so the tree can be cut at any aligned power-of-two subtree:
+//   lane        an aligned run of R consecutive slots, pairwise in registers                       (mom_lane_tree)
+//   wave        xor butterfly over the 64 lanes: lane l and lane l ^ s add the same two numbers     (mom_block_tree)
+//   workgroup   the 4 waves through LDS: (w0 + w1) + (w2 + w3) -> ONE partial per aligned run of 256 R slots
+//   launch      k_mom_tree sums aligned runs of 1024 partials the same way, repeated until one value is left
+// No floating-point atomics, no ticket: the combine over partials is a further launch on the same stream, so the result is a pure
+// function of the stored values on any launch geometry.  The max of the log-weights is exact in any order and takes the same kernels.
+//
+// Particle filter (mp_pf_moments): m = max lw;  a_i = lw_i == -inf ? 0 : mp_exp(lw_i - m);  A = TREE(a);
+//   mean_j = TREE(a_i x_ij) / A;   c_ij = x_ij - mean_j;   cov_jk = TREE(a_i (c_ij c_ik)) / A   (k <= j; the other half is a copy)
+// Three passes (max, first moment, centred second moment); no one-pass covariance.
+// MH chains of a registered function (mp_mh_site_moments), per site s with presence bit p_i:
+//   count_s = TREE(p_i) (a sum of 0.0 / 1.0: exact);  mean_s = TREE(p_i ? v_i : +0.0) / count_s;
+//   var_s = TREE(p_i ? (v_i - mean_s)^2 : +0.0) / count_s      (selected, never multiplied: a stale NaN in an absent slot cannot leak)
+//
+// Registers (gfx950 code object, kernel-resource-usage): k_mom_pf2<16> holds c[R = 4][16] and a[4] per lane and walks the 136 (j, k)
+// pairs one at a time — one accumulator tree per pair, never 136 live accumulators; see DESIGN.md §5 for the VGPR / scratch figures.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "mp_math.h"
+
+#define MOM_THREADS 256
+#define MOM_WAVES (MOM_THREADS / 64)
+#define MOM_TREE_R 4                          // k_mom_tree: inputs per lane
+#define MOM_TREE_RUN (MOM_THREADS * MOM_TREE_R)   // ... and per workgroup
+#define MOM_MAX_DIM 16                        // the widest compiled model
+#define MOM_MAX_COLS (MOM_MAX_DIM * (MOM_MAX_DIM + 1) / 2)
+
+struct mom_add { __device__ __forceinline__ static double id() { return 0.; } __device__ __forceinline__ static double op(double a, double b) { return a + b; } };
+// (a NaN wins from either side, so the max stays a function of the set of values: a NaN log-weight gives m = NaN, as numpy's max does)
+struct mom_max { __device__ __forceinline__ static double id() { return -MP_INF; } __device__ __forceinline__ static double op(double a, double b) { return (a > b || a != a) ? a : b; } };
+
+// slots per lane of the level-0 kernels for a state width D (the compiled models' 1, 2, 4 or 16): R * D <= 64 doubles of centred state per lane
+template <int D> struct mom_run { static constexpr int R = D <= 4 ? 8 : 4; };
+
+// TREE of the lane's R values (R a power of two), in registers
+template <class Op, int R>
+__device__ __forceinline__ double mom_lane_tree(double (&t)[R]) {
+#pragma unroll
+    for (int w = R; w > 1; w >>= 1) {
+#pragma unroll
+        for (int i = 0; i < w / 2; ++i) t[i] = Op::op(t[2 * i], t[2 * i + 1]);
+    }
+    return t[0];
+}
+// the wave's subtree: after step s every lane holds the sum of its aligned group of 2 s lanes (both partners add the same two numbers)
+template <class Op>
+__device__ __forceinline__ double mom_wave_tree(double v) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) v = Op::op(v, __shfl_xor(v, s, 64));
+    return v;
+}
+// column `col` of a workgroup: every wave leaves its subtree in s_part[col][wave]; after ONE __syncthreads mom_block_combine closes the tree
+template <class Op>
+__device__ __forceinline__ void mom_block_put(double v, int col, double* s_part) {
+    v = mom_wave_tree<Op>(v);
+    if ((threadIdx.x & 63) == 0) s_part[col * MOM_WAVES + (threadIdx.x >> 6)] = v;
+}
+template <class Op>
+__device__ __forceinline__ double mom_block_combine(int col, const double* s_part) {
+    const double* p = s_part + col * MOM_WAVES;
+    return Op::op(Op::op(p[0], p[1]), Op::op(p[2], p[3]));
+}
+
+// ---- the combine over partials: out[c][b] = TREE(in[c][1024 b .. 1024 b + 1024)), missing entries = the identity -------------------
+template <class Op>
+__global__ __launch_bounds__(MOM_THREADS) void k_mom_tree(const double* __restrict__ in, unsigned long long n_in, double* __restrict__ out, unsigned long long n_out) {
+    __shared__ double s_part[MOM_WAVES];
+    const unsigned long long c = blockIdx.y;
+    const unsigned long long i0 = (unsigned long long)blockIdx.x * MOM_TREE_RUN + (unsigned long long)threadIdx.x * MOM_TREE_R;
+    double t[MOM_TREE_R];
+#pragma unroll
+    for (int r = 0; r < MOM_TREE_R; ++r) t[r] = (i0 + r < n_in) ? in[c * n_in + i0 + r] : Op::id();
+    mom_block_put<Op>(mom_lane_tree<Op, MOM_TREE_R>(t), 0, s_part);
+    __syncthreads();
+    if (threadIdx.x == 0) out[c * n_out + blockIdx.x] = mom_block_combine<Op>(0, s_part);
+}
+
+#ifdef MP_MOMENTS_PF   // (mp_pf.hip)
+// ---- pass 0: partial maxima of a column of n doubles -------------------------------------------------------------------------------
+__global__ __launch_bounds__(MOM_THREADS) void k_mom_max0(unsigned long long n, const double* __restrict__ lw, double* __restrict__ out) {
+    constexpr int R = 8;
+    __shared__ double s_part[MOM_WAVES];
+    const unsigned long long i0 = ((unsigned long long)blockIdx.x * MOM_THREADS + threadIdx.x) * R;
+    double t[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) t[r] = (i0 + r < n) ? lw[i0 + r] : -MP_INF;
+    mom_block_put<mom_max>(mom_lane_tree<mom_max, R>(t), 0, s_part);
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = mom_block_combine<mom_max>(0, s_part);
+}
+
+__device__ __forceinline__ double mom_weight(double lw, double m) { return lw == -MP_INF ? 0. : mp_exp(lw - m); }
+
+// ---- particle filter, pass 1: out[0][b] = subtree of a_i, out[1 + j][b] = subtree of a_i x_ij; nb = gridDim.x -------------------------
+// DP = dim_state: a lane's R rows are R * DP consecutive doubles at a compile-time stride (wide loads).
+template <int DP>
+__global__ __launch_bounds__(MOM_THREADS) void k_mom_pf1(unsigned long long n, const double* __restrict__ x, const double* __restrict__ lw,
+                                                         const double* __restrict__ m_ptr, double* __restrict__ out) {
+    constexpr int R = mom_run<DP>::R;
+    __shared__ double s_part[(DP + 1) * MOM_WAVES];
+    constexpr int d = DP;
+    const double m = *m_ptr;
+    const unsigned long long i0 = ((unsigned long long)blockIdx.x * MOM_THREADS + threadIdx.x) * R;
+    double a[R], xv[R][DP], t[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int j = 0; j < DP; ++j) xv[r][j] = (i0 + r < n && j < d) ? x[(i0 + r) * (unsigned long long)d + j] : 0.;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) a[r] = (i0 + r < n) ? mom_weight(lw[i0 + r], m) : 0.;
+#pragma unroll
+    for (int r = 0; r < R; ++r) t[r] = a[r];
+    mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(t), 0, s_part);
+#pragma unroll
+    for (int j = 0; j < DP; ++j) {
+        if (j < d) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) t[r] = (i0 + r < n) ? a[r] * xv[r][j] : 0.;
+            mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(t), 1 + j, s_part);
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x <= d) out[(unsigned long long)threadIdx.x * gridDim.x + blockIdx.x] = mom_block_combine<mom_add>((int)threadIdx.x, s_part);
+}
+
+// ---- particle filter, pass 2: column j (j + 1) / 2 + k (k <= j) = subtree of a_i ((x_ij - mean_j) (x_ik - mean_k)) ------------------------
+// sums = the closed trees of pass 1 ({A, S_0 .. S_{d-1}}); every lane forms mean_j = S_j / A itself (same bits), workgroup 0 stores it.
+template <int DP>
+__global__ __launch_bounds__(MOM_THREADS) void k_mom_pf2(unsigned long long n, const double* __restrict__ x, const double* __restrict__ lw,
+                                                         const double* __restrict__ m_ptr, const double* __restrict__ sums, double* __restrict__ mean_out,
+                                                         double* __restrict__ out) {
+    constexpr int R = mom_run<DP>::R;
+    __shared__ double s_part[(DP * (DP + 1) / 2) * MOM_WAVES];
+    constexpr int d = DP;
+    const double m = *m_ptr;
+    const double A = sums[0];
+    const unsigned long long i0 = ((unsigned long long)blockIdx.x * MOM_THREADS + threadIdx.x) * R;
+    double a[R], c[R][DP], t[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int j = 0; j < DP; ++j) c[r][j] = (i0 + r < n && j < d) ? x[(i0 + r) * (unsigned long long)d + j] : 0.;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) a[r] = (i0 + r < n) ? mom_weight(lw[i0 + r], m) : 0.;
+#pragma unroll
+    for (int j = 0; j < DP; ++j) {
+        if (j < d) {
+            const double mean = sums[1 + j] / A;
+            if (blockIdx.x == 0 && threadIdx.x == 0) mean_out[j] = mean;
+#pragma unroll
+            for (int r = 0; r < R; ++r) c[r][j] = (i0 + r < n) ? c[r][j] - mean : 0.;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < DP; ++j) {
+#pragma unroll
+        for (int k = 0; k <= j; ++k) {
+            if (j < d) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) t[r] = (i0 + r < n) ? a[r] * (c[r][j] * c[r][k]) : 0.;
+                mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(t), j * (j + 1) / 2 + k, s_part);
+            }
+        }
+    }
+    __syncthreads();
+    const int ncols = d * (d + 1) / 2;
+    if ((int)threadIdx.x < ncols) out[(unsigned long long)threadIdx.x * gridDim.x + blockIdx.x] = mom_block_combine<mom_add>((int)threadIdx.x, s_part);
+}
+
+#endif   // MP_MOMENTS_PF
+
+#ifdef MP_MOMENTS_MH   // (mp_mh.hip)
+// ---- MH chains of a registered function: vals[site][chain], present[word][chain]; one grid row per site ------------------------------------
+// pass 1: out[2 s][b] = subtree of (p_i ? v_i : +0.0), out[2 s + 1][b] = subtree of p_i
+__global__ __launch_bounds__(MOM_THREADS) void k_mom_site1(unsigned long long n, const double* __restrict__ vals, const uint32_t* __restrict__ present,
+                                                           double* __restrict__ out) {
+    constexpr int R = 8;
+    __shared__ double s_part[2 * MOM_WAVES];
+    const unsigned int s = blockIdx.y;
+    const unsigned long long i0 = ((unsigned long long)blockIdx.x * MOM_THREADS + threadIdx.x) * R;
+    double tv[R], tp[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const bool p = (i0 + r < n) && ((present[(unsigned long long)(s >> 5) * n + i0 + r] >> (s & 31u)) & 1u);
+        tv[r] = p ? vals[(unsigned long long)s * n + i0 + r] : 0.;
+        tp[r] = p ? 1. : 0.;
+    }
+    mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(tv), 0, s_part);
+    mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(tp), 1, s_part);
+    __syncthreads();
+    if (threadIdx.x < 2) out[(unsigned long long)(2 * s + threadIdx.x) * gridDim.x + blockIdx.x] = mom_block_combine<mom_add>((int)threadIdx.x, s_part);
+}
+// pass 2: out[s][b] = subtree of (p_i ? (v_i - mean_s)^2 : +0.0), mean_s = sums[2 s] / sums[2 s + 1] (0 / 0 = NaN for a site nobody has: no term is selected)
+__global__ __launch_bounds__(MOM_THREADS) void k_mom_site2(unsigned long long n, const double* __restrict__ vals, const uint32_t* __restrict__ present,
+                                                           const double* __restrict__ sums, double* __restrict__ mean_out, double* __restrict__ out) {
+    constexpr int R = 8;
+    __shared__ double s_part[MOM_WAVES];
+    const unsigned int s = blockIdx.y;
+    const double mean = sums[2 * s] / sums[2 * s + 1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) mean_out[s] = mean;
+    const unsigned long long i0 = ((unsigned long long)blockIdx.x * MOM_THREADS + threadIdx.x) * R;
+    double t[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const bool p = (i0 + r < n) && ((present[(unsigned long long)(s >> 5) * n + i0 + r] >> (s & 31u)) & 1u);
+        const double c = p ? vals[(unsigned long long)s * n + i0 + r] - mean : 0.;
+        t[r] = p ? c * c : 0.;
+    }
+    mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(t), 0, s_part);
+    __syncthreads();
+    if (threadIdx.x == 0) out[(unsigned long long)s * gridDim.x + blockIdx.x] = mom_block_combine<mom_add>(0, s_part);
+}
+
+#endif   // MP_MOMENTS_MH
+
+// ---- host side: close the trees of `cols` columns of `nb` partials each ([cols][nb] in buf[0]) into dst[cols] -----------------------------
+// buf[0] holds cols * nb doubles, buf[1] cols * ceil(nb / 1024).  At least one launch: a single partial goes through the tree as v + 0.
+template <class Op>
+static inline void mom_close(hipStream_t stream, double* const buf[2], unsigned long long nb, unsigned cols, double* dst) {
+    int cur = 0;
+    for (;;) {
+        const unsigned long long nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
+        hipLaunchKernelGGL(k_mom_tree<Op>, dim3((unsigned)nn, cols), dim3(MOM_THREADS), 0, stream, (const double*)buf[cur], nb, nn == 1 ? dst : buf[cur ^ 1], nn);
+        if (nn == 1) return;
+        nb = nn;
+        cur ^= 1;
+    }
+}

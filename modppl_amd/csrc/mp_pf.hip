@@ -74,6 +74,8 @@ int32_t mp_set_error(int32_t code, const std::string& msg) { return mp_fail(code
 #include "mp_pf_kernels.h"
 #include "mp_pf_k1mt.h"
 #include "mp_pf_shard_kernels.h"
+#define MP_MOMENTS_PF
+#include "mp_moments.h"   // mp_pf_moments: the tree reduction and its kernels (after every existing kernel)
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -556,6 +558,10 @@ struct mp_pf {
     size_t hist_slab_left = 0, hist_slab_next = 0;
     mp_dev<mp_hist_event> d_hist_events;   // device copy of the log for k_trajectories
     size_t d_hist_events_cap = 0;
+    // mp_pf_moments (mp_moments.h), allocated on first use: partials of one pass ([columns][workgroups], two levels), the closed trees
+    mp_dev<double> mom_buf[2];
+    mp_dev<double> mom_res;                // {m, A, S[d], mean[d], C[d (d + 1) / 2]}
+    mp_pinned<double> mom_host;            // ... and where they land on the host
     // host-side filter state
     long long t = 0;  // Unfold steps taken (trace.args.0)
     uint32_t resample_count = 0;
@@ -917,6 +923,17 @@ static int32_t ensure_rows(mp_pf* h) {
 }
 
 static int32_t shard_scratch(mp_pf* h, int world, u64 cap);
+
+// mp_pf_moments: one level-0 launch of pass 1 (first moments) or 2 (centred second moments) for a state width D
+template <int D>
+static void launch_moments_pass(mp_pf* h, int pass, unsigned nb, const double* x, double* res) {
+    if (pass == 1)
+        hipLaunchKernelGGL((k_mom_pf1<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, x, (const double*)h->logw, (const double*)res,
+                           h->mom_buf[0].get());
+    else
+        hipLaunchKernelGGL((k_mom_pf2<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, x, (const double*)h->logw, (const double*)res,
+                           (const double*)(res + 1), res + 2 + D, h->mom_buf[0].get());
+}
 
 extern "C" {
 
@@ -1370,6 +1387,64 @@ int32_t mp_pf_read_parents(mp_pf* h, uint32_t* out) {
     }
     HIPCK(hipMemcpyAsync(out, h->parent, sizeof(uint32_t) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
+    return MP_OK;
+}
+
+// Weighted mean and covariance of the particle cloud, reduced on the device: replaces the host-side reduction a caller of the reference
+// writes over its public `traces` / `log_weights` fields (particle_filter.rs:13-20) — here mp_pf_read_state + mp_pf_read_log_weights
+// and a loop.  Definition (the tree sum, relative to the global max log-weight): mp_moments.h, DESIGN.md section 4.
+// All launches are enqueued before the one wait, so a cloud whose log-weights are all -inf still pays for every pass (its weights are
+// selected to 0 and nothing is returned but the status): looking at m after the max pass would cost every healthy call a second wait.
+int32_t mp_pf_moments(mp_pf* h, double* mean_out, double* cov_out) {
+    if (!h || !mean_out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
+    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_moments: one shard of a larger world (n_global != n_particles); the moments of a sharded job need an all-reduce of the max and an all-gather of the partials");
+    if (!h->initialised) return mp_fail(MP_ERR_STATE, "moments before init_step");
+    const int d = h->ops->dim_state;
+    if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_moments: no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
+    HIPCK(hipSetDevice(h->device));
+    { int32_t rcm = materialize(h); if (rcm != MP_OK) return rcm; }
+    { int32_t rcx = ensure_x(h); if (rcx != MP_OK) return rcx; }
+    { int32_t rcl = ensure_lazy(h); if (rcl != MP_OK) return rcl; }
+    const int R = d <= 4 ? 8 : 4;   // mom_run<D>::R
+    const int npairs = d * (d + 1) / 2;
+    const u64 nb = (h->n + (u64)MOM_THREADS * R - 1) / ((u64)MOM_THREADS * R);          // workgroups of the two moment passes
+    const u64 nb_max = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);      // ... and of the max pass (<= nb)
+    const size_t n_res = 2 + 2 * (size_t)d + npairs;
+    if (!h->mom_res) {
+        const size_t cols = (size_t)std::max(d + 1, npairs);
+        HIPCK(mp_hipMalloc(h->mom_buf[0], cols * nb));
+        HIPCK(mp_hipMalloc(h->mom_buf[1], cols * ((nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN)));
+        HIPCK(mp_hipHostMalloc(h->mom_host, n_res));
+        HIPCK(mp_hipMalloc(h->mom_res, n_res));
+    }
+    double* const buf[2] = {h->mom_buf[0].get(), h->mom_buf[1].get()};
+    double* res = h->mom_res;
+    const double* x = h->x[h->cur];
+    hipLaunchKernelGGL(k_mom_max0, dim3((unsigned)nb_max), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->logw, buf[0]);
+    mom_close<mom_max>(h->stream, buf, nb_max, 1, res);
+    for (int pass = 1; pass <= (cov_out ? 2 : 1); ++pass) {
+        switch (d) {
+        case 1: launch_moments_pass<1>(h, pass, (unsigned)nb, x, res); break;
+        case 2: launch_moments_pass<2>(h, pass, (unsigned)nb, x, res); break;
+        case 4: launch_moments_pass<4>(h, pass, (unsigned)nb, x, res); break;
+        default: launch_moments_pass<16>(h, pass, (unsigned)nb, x, res); break;
+        }
+        mom_close<mom_add>(h->stream, buf, nb, pass == 1 ? (unsigned)(d + 1) : (unsigned)npairs, pass == 1 ? res + 1 : res + 2 + 2 * d);
+    }
+    { int32_t rck = check_launch("mp_pf_moments kernels"); if (rck != MP_OK) return rck; }
+    HIPCK(hipMemcpyAsync(h->mom_host, res, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(stream_wait(h->stream));
+    const double* r = h->mom_host;
+    if (r[0] == -MP_INF)
+        return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+    const double A = r[1];
+    // without a covariance pass nobody has formed the means on the device: the same IEEE division here
+    for (int j = 0; j < d; ++j) mean_out[j] = cov_out ? r[2 + d + j] : r[2 + j] / A;
+    if (cov_out) {
+        const double* C = r + 2 + 2 * d;
+        for (int j = 0; j < d; ++j)
+            for (int k = 0; k <= j; ++k) cov_out[j * d + k] = cov_out[k * d + j] = C[j * (j + 1) / 2 + k] / A;
+    }
     return MP_OK;
 }
 

@@ -181,6 +181,13 @@ class HipShardEngine:
         capi.check(self._L.mp_pf_read_log_weights(self._h, w.ctypes.data_as(C.POINTER(C.c_double))))
         return w
 
+    def moments(self, cov=True):
+        d = self.model.dim_state
+        mean = np.empty(d)
+        c = np.empty((d, d)) if cov else None
+        capi.check(self._L.mp_pf_moments(self._h, mean.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_double)) if cov else None))
+        return mean, c
+
     def parents(self):
         p = np.empty(self.n, dtype=np.uint32)
         capi.check(self._L.mp_pf_read_parents(self._h, p.ctypes.data_as(C.POINTER(C.c_uint32))))
@@ -683,6 +690,12 @@ class ShardedParticleSystem:
     @property
     def parents(self):
         return self.engine.parents()
+
+    def moments(self, cov=True):
+        """-> (mean, cov or None) of the cloud, reduced on the device (ParticleSystem.moments).  A world of one only: one shard of a
+        larger world raises the library's MP_ERR_UNSUPPORTED (the sharded form needs an all-reduce of the max log-weight and an
+        all-gather of the tile partials)."""
+        return self.engine.moments(cov)
 
     def synchronize(self):
         self.engine.synchronize()

@@ -145,6 +145,16 @@ class ParticleSystem:
         capi.check(self._L.mp_pf_read_log_weights(self._h, _dptr(w)))
         return w
 
+    def moments(self, cov=True):
+        """-> (mean [dim_state], cov [dim_state, dim_state] or None): the weighted mean and (population) covariance of the cloud under
+        the current log-weights, reduced on the device (mp_pf_moments) — what `states()` + `log_weights` and a host-side reduction give,
+        without moving the particles.  The sums are pairwise trees over slot ids: same bits on every call."""
+        d = self.model.dim_state
+        mean = np.empty(d)
+        c = np.empty((d, d)) if cov else None
+        capi.check(self._L.mp_pf_moments(self._h, _dptr(mean), _dptr(c) if cov else None))
+        return mean, c
+
     @property
     def parents(self):
         p = np.empty(self.num_particles, dtype=np.uint32)
@@ -336,6 +346,11 @@ class HierarchicalChains:
         capi.check(self._L.mp_regen_mh_step(self._h, m if sites else None, len(sites), int(cycle), int(n_iters), C.byref(acc)))
         return acc.value
 
+    def site_moments(self, var=True):
+        """registered-function chains only (functor=True): FunctionChains.site_moments; the hand-written kernels keep no trace table
+        (MP_ERR_UNSUPPORTED, as for mp_mh_read_trace)"""
+        return _site_moments(self._L, self._h, var)
+
     def states(self):
         """[num_chains, 4] = is_linear, a, b, c  (read_coeffs of hierarchical.rs:5-16)."""
         if self._fn is not None:
@@ -380,6 +395,16 @@ class HierarchicalChains:
             self.close()
         except Exception:
             pass
+
+
+def _site_moments(L, h, var):
+    ns = C.c_int32()
+    capi.check(L.mp_mh_n_sites(h, C.byref(ns)))   # (hand-written chains stop here: MP_ERR_UNSUPPORTED)
+    count = np.empty(ns.value, dtype=np.uint64)
+    mean = np.empty(ns.value)
+    v = np.empty(ns.value) if var else None
+    capi.check(L.mp_mh_site_moments(h, count.ctypes.data_as(C.POINTER(C.c_uint64)), _dptr(mean), _dptr(v) if var else None))
+    return count, mean, v
 
 
 def _fn_constraints(constraints):
@@ -512,6 +537,11 @@ class FunctionChains:
         capi.check(self._L.mp_mh_read_trace(self._h, _dptr(vals), present.ctypes.data_as(C.POINTER(C.c_uint32))))
         return vals, self._present_out(present)
 
+    def site_moments(self, var=True):
+        """-> (count [num_sites] uint64, mean [num_sites], var [num_sites] or None): per site, over the chains whose trace holds it, reduced
+        on the device (mp_mh_site_moments) — what trace() and a host-side mean over chains give.  A site no chain holds: count 0, NaN."""
+        return _site_moments(self._L, self._h, var)
+
     # ---- the GFI operations one at a time (modppl/src/gfi.rs:57-90), every chain per call ------------------------------------
     # constraints: {site: value} shared by all chains, or a (values [num_chains, num_sites], present [num_chains]) pair per chain
     # (what propose() and update()'s discard return).  rng_step = 0: the next MH iteration's Philox step, which the call consumes.
@@ -619,6 +649,12 @@ class PointedChains:
         acc = C.c_uint64()
         capi.check(self._L.mp_mh_step(self._h, capi.MP_MH_PROPOSAL_POINTED_DRIFT, _dptr(nz), 4, int(n_iters), C.byref(acc)))
         return acc.value
+
+    def site_moments(self, var=True):
+        """registered-function chains only (functor=True); the hand-written kernels keep no trace table (MP_ERR_UNSUPPORTED)"""
+        if self._fn is not None:
+            return self._fn.site_moments(var)
+        return _site_moments(self._L, self._h, var)
 
     def states(self):
         """[num_chains, 2] = latent."""

@@ -82,6 +82,7 @@ extern "C" {
     pub fn mp_pf_read_state(h: *mut mp_pf, x_out: *mut f64) -> i32;
     pub fn mp_pf_read_log_weights(h: *mut mp_pf, out: *mut f64) -> i32;
     pub fn mp_pf_read_parents(h: *mut mp_pf, out: *mut u32) -> i32;
+    pub fn mp_pf_moments(h: *mut mp_pf, mean_out: *mut f64, cov_out: *mut f64) -> i32;
     pub fn mp_pf_read_trajectory(h: *mut mp_pf, i: u64, out: *mut f64, t_steps: *mut i32) -> i32;
     pub fn mp_pf_read_trajectories(h: *mut mp_pf, first: u64, count: u64, out: *mut f64, t_steps: *mut i32) -> i32;
     pub fn mp_pf_time(h: *mut mp_pf, out: *mut i64) -> i32;
@@ -151,6 +152,7 @@ extern "C" {
                            n_constraints: i32, n_chains: u64, seed: u64, device: i32, stream: *mut c_void, out: *mut *mut mp_mh) -> i32;
     pub fn mp_mh_n_sites(h: *mut mp_mh, out: *mut i32) -> i32;
     pub fn mp_mh_read_trace(h: *mut mp_mh, values: *mut f64, present: *mut u32) -> i32;
+    pub fn mp_mh_site_moments(h: *mut mp_mh, count_out: *mut u64, mean_out: *mut f64, var_out: *mut f64) -> i32;
     pub fn mp_fn_update(h: *mut mp_mh, argdiff: i32, rng_step: u32, sites: *const i32, values: *const f64, n_constraints: i32,
                         chain_values: *const f64, chain_present: *const u32, weights_out: *mut f64, discard_values_out: *mut f64,
                         discard_present_out: *mut u32) -> i32;

@@ -83,6 +83,14 @@ impl ParticleSystem {
         check(unsafe { sys::mp_pf_resample_if_ess_below(self.h, scheme, ess_fraction, &mut did, &mut ess, &mut ltw) });
         (did != 0, ess)
     }
+    /// Weighted mean `[dim_state]` and population covariance `[dim_state][dim_state]` (row-major) of the cloud, reduced on the device:
+    /// the host-side reduction over `states()` and `log_weights()` without moving the particles.
+    pub fn moments(&self) -> (Vec<f64>, Vec<f64>) {
+        let d = self.model.dim_state as usize;
+        let (mut mean, mut cov) = (vec![0.0; d], vec![0.0; d * d]);
+        check(unsafe { sys::mp_pf_moments(self.h, mean.as_mut_ptr(), cov.as_mut_ptr()) });
+        (mean, cov)
+    }
     /// `log_weights` (pub field of the reference's struct)
     pub fn log_weights(&self) -> Vec<f64> {
         let mut w = vec![0.0; self.num_particles];
@@ -286,6 +294,13 @@ impl FunctionChains {
         let mut p = vec![0u32; self.n_chains * self.words()];
         check(unsafe { sys::mp_mh_read_trace(self.h, v.as_mut_ptr(), p.as_mut_ptr()) });
         (v, p)
+    }
+    /// Per site, over the chains whose trace holds it: `(count, mean, population variance)`, reduced on the device; a site no chain
+    /// holds has count 0 and NaN moments.
+    pub fn site_moments(&self) -> (Vec<u64>, Vec<f64>, Vec<f64>) {
+        let (mut c, mut m, mut v) = (vec![0u64; self.n_sites], vec![0.0; self.n_sites], vec![0.0; self.n_sites]);
+        check(unsafe { sys::mp_mh_site_moments(self.h, c.as_mut_ptr(), m.as_mut_ptr(), v.as_mut_ptr()) });
+        (c, m, v)
     }
     // ---- `GenFn::update / regenerate / assess / propose` (gfi.rs:57-90) one at a time, every chain per call ----
     /// `(new_trace, discard, weight) = model.update(trace, args, diff, constraints)` with per-chain constraints
