@@ -23,6 +23,7 @@
 
 #include "../../include/modppl_hip.h"
 #include "mp_dists.h"
+#include "mp_err.h"
 #include "mp_hip_own.h"
 #include "mp_linalg.h"
 
@@ -30,18 +31,9 @@ typedef unsigned long long u64;
 #define MH_MAX_DATA 16
 #define MH_THREADS 256
 
-static thread_local std::string g_mh_err;
-extern "C" const char* mp_last_error(void);
-int32_t mp_set_error(int32_t code, const std::string& msg);  // mp_pf.hip
 // mp_pf.hip: L, log-ML, lnw[n] and M categorical draws from a device array of log-weights (importance.rs:21-27, 44-47)
 int32_t mp_is_finish_device(const double* d_logw, uint64_t n, uint64_t num_ret, uint64_t seed, int32_t device, void* stream, double* log_ml_estimate,
                             double* log_normalized_weights, uint64_t* resampled_indices);
-#define MHCK(call)                                                                                   \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) return mp_set_error(MP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct mh_data {
     int n;
     double xs[MH_MAX_DATA], ys[MH_MAX_DATA];
@@ -418,8 +410,8 @@ struct mp_mh {           // (every device pointer is a holder, mp_hip_own.h; the
 static int32_t mh_finish(mp_mh* h, uint64_t* accepted) {
     if (!accepted && !h->fn) return MP_OK;
     u64 tot[2] = {0, 0};
-    MHCK(hipMemcpyAsync(tot, h->d_acc, sizeof(u64) * (h->fn ? 2 : 1), hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipStreamSynchronize(h->stream));
+    HIPCK(hipMemcpyAsync(tot, h->d_acc, sizeof(u64) * (h->fn ? 2 : 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
     if (accepted) *accepted = tot[0];
     if (tot[1])
         return mp_set_error(MP_ERR_STATE, std::to_string(tot[1]) + " chain-moves reached a case the reference panics on: constraints nobody consumed "
@@ -449,27 +441,27 @@ int32_t mp_mh_create(int32_t model_kind, const double* xs, const double* ys, int
     h->data.n = n_data;
     for (int k = 0; k < MH_MAX_DATA; ++k) { h->data.xs[k] = k < n_data ? xs[k] : 0.; h->data.ys[k] = k < n_data ? ys[k] : 0.; }
     h->ln_noise = mp_log(MH_NOISE);
-    MHCK(hipSetDevice(device));
+    HIPCK(hipSetDevice(device));
     if (stream) h->stream.borrow((hipStream_t)stream);
-    else MHCK(h->stream.create(hipStreamNonBlocking));
-    MHCK(mp_hipMalloc(h->is_lin, n_chains));
-    MHCK(mp_hipMalloc(h->a, n_chains));
-    MHCK(mp_hipMalloc(h->b, n_chains));
-    MHCK(mp_hipMalloc(h->c, n_chains));
-    MHCK(mp_hipMalloc(h->tmp, n_chains * 4));
-    MHCK(mp_hipMalloc(h->d_acc, 1));
+    else HIPCK(h->stream.create(hipStreamNonBlocking));
+    HIPCK(mp_hipMalloc(h->is_lin, n_chains));
+    HIPCK(mp_hipMalloc(h->a, n_chains));
+    HIPCK(mp_hipMalloc(h->b, n_chains));
+    HIPCK(mp_hipMalloc(h->c, n_chains));
+    HIPCK(mp_hipMalloc(h->tmp, n_chains * 4));
+    HIPCK(mp_hipMalloc(h->d_acc, 1));
     hipLaunchKernelGGL(k_mh_init, dim3((unsigned)((n_chains + MH_THREADS - 1) / MH_THREADS)), dim3(MH_THREADS), 0, h->stream, h->n,
                        (uint32_t)seed, (uint32_t)(seed >> 32), constrain_is_linear, h->is_lin, h->a, h->b, h->c);
-    MHCK(hipGetLastError());
-    MHCK(hipStreamSynchronize(h->stream));
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(h->stream));
     *out = h.release();
     return MP_OK;
 }
 
 static int32_t mh_run(mp_mh* h, int kind, const mh_mask& mask, double drift_std, int32_t n_iters, uint64_t* accepted) {
     if (n_iters < 0) return mp_set_error(MP_ERR_INVALID_ARG, "n_iters < 0");
-    MHCK(hipSetDevice(h->device));
-    MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64), h->stream));
+    HIPCK(hipSetDevice(h->device));
+    HIPCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64), h->stream));
     const unsigned grid = (unsigned)((h->n + MH_THREADS - 1) / MH_THREADS);
     const uint32_t iter0 = (uint32_t)(h->iters + 1);
     const double ln_ds = kind ? mp_log(drift_std) : 0.;
@@ -482,11 +474,11 @@ static int32_t mh_run(mp_mh* h, int kind, const mh_mask& mask, double drift_std,
     else
         hipLaunchKernelGGL(k_mh_iterate<0>, dim3(grid), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), iter0,
                            n_iters, h->data, h->ln_noise, mask, drift_std, ln_ds, mp_rcp_hoist(drift_std), h->is_lin, h->a, h->b, h->c, h->d_acc, (const double*)h->ys_chain);
-    MHCK(hipGetLastError());
+    HIPCK(hipGetLastError());
     h->iters += (u64)n_iters;
     if (accepted) {
-        MHCK(hipMemcpyAsync(accepted, h->d_acc, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-        MHCK(hipStreamSynchronize(h->stream));
+        HIPCK(hipMemcpyAsync(accepted, h->d_acc, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));
     }
     return MP_OK;
 }
@@ -517,15 +509,15 @@ int32_t mp_mh_create_pointed(const double* bounds, const double* obs_cov, const 
     for (int q = 0; q < 4; ++q) P.cov_inv[q] = inv[q];
     P.ln_det_cov = mp_log(det);
     P.obs[0] = obs[0]; P.obs[1] = obs[1];
-    MHCK(hipSetDevice(device));
+    HIPCK(hipSetDevice(device));
     if (stream) h->stream.borrow((hipStream_t)stream);
-    else MHCK(h->stream.create(hipStreamNonBlocking));
-    MHCK(mp_hipMalloc(h->lat, 2 * n_chains));
-    MHCK(mp_hipMalloc(h->tmp, n_chains));
-    MHCK(mp_hipMalloc(h->d_acc, 1));
+    else HIPCK(h->stream.create(hipStreamNonBlocking));
+    HIPCK(mp_hipMalloc(h->lat, 2 * n_chains));
+    HIPCK(mp_hipMalloc(h->tmp, n_chains));
+    HIPCK(mp_hipMalloc(h->d_acc, 1));
     hipLaunchKernelGGL(k_pointed_init, dim3((unsigned)((n_chains + MH_THREADS - 1) / MH_THREADS)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)seed,
                        (uint32_t)(seed >> 32), P, h->lat);
-    MHCK(hipGetLastError());
+    HIPCK(hipGetLastError());
     *out = h.release();
     return MP_OK;
 }
@@ -550,15 +542,15 @@ static int32_t fn_alloc(int32_t model_kind, const double* params, int32_t n_para
     h->kind = model_kind;
     h->fn = ops;
     h->n = n_chains; h->seed = seed; h->device = device;
-    MHCK(hipSetDevice(device));
+    HIPCK(hipSetDevice(device));
     if (stream) h->stream.borrow((hipStream_t)stream);
-    else MHCK(h->stream.create(hipStreamNonBlocking));
-    MHCK(mp_hipMalloc(h->fvals, n_chains * 2 * (size_t)ops->ns()));   // [n_sites] values + [n_sites] sub-trie running weights (rows of sub-call ids)
-    MHCK(mp_hipMalloc(h->fpresent, n_chains * (size_t)fn_words(ops->ns())));
-    MHCK(mp_hipMalloc(h->tmp, n_chains));
-    MHCK(mp_hipMalloc(h->d_acc, 2));
-    MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
-    MHCK(hipMemsetAsync(h->fpresent, 0, sizeof(uint32_t) * n_chains * (size_t)fn_words(ops->ns()), h->stream));
+    else HIPCK(h->stream.create(hipStreamNonBlocking));
+    HIPCK(mp_hipMalloc(h->fvals, n_chains * 2 * (size_t)ops->ns()));   // [n_sites] values + [n_sites] sub-trie running weights (rows of sub-call ids)
+    HIPCK(mp_hipMalloc(h->fpresent, n_chains * (size_t)fn_words(ops->ns())));
+    HIPCK(mp_hipMalloc(h->tmp, n_chains));
+    HIPCK(mp_hipMalloc(h->d_acc, 2));
+    HIPCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
+    HIPCK(hipMemsetAsync(h->fpresent, 0, sizeof(uint32_t) * n_chains * (size_t)fn_words(ops->ns()), h->stream));
     out = std::move(h);
     return MP_OK;
 }
@@ -576,8 +568,7 @@ static int32_t fn_shared_constraints(int ns, const int32_t* sites, const double*
 // N x model.generate(args, constraints) at Philox step 0 (tests/mh.rs:91, importance.rs:18-20): the weights stay in h->tmp
 static int32_t fn_create_generate(int32_t model_kind, const double* params, int32_t n_params, const int32_t* constraint_sites, const double* constraint_values,
                                   int32_t n_constraints, uint64_t n_chains, uint64_t seed, int32_t device, void* stream, std::unique_ptr<mp_mh, mh_cleanup>& h) {
-    int32_t rc = fn_alloc(model_kind, params, n_params, n_chains, seed, device, stream, h);
-    if (rc != MP_OK) return rc;
+    MPCK(fn_alloc(model_kind, params, n_params, n_chains, seed, device, stream, h));
     if (n_constraints < 0 || (n_constraints > 0 && (!constraint_sites || !constraint_values))) return mp_set_error(MP_ERR_INVALID_ARG, "bad constraints");
     // declared data sites (mp_genfn.h): observation j is site id ns + j here and nowhere else — its value goes into a shared array
     const int ns = h->fn->ns(), nd = h->fn->n_data();
@@ -600,17 +591,15 @@ static int32_t fn_create_generate(int32_t model_kind, const double* params, int3
             if (!seen[(size_t)j])
                 return mp_set_error(MP_ERR_UNSUPPORTED, "every declared data site must be constrained (an observation drawn from its prior would be per-chain state: "
                                                         "write the model with ordinary sites for that)");
-        MHCK(mp_hipMalloc(h->d_data, buf.size()));
-        MHCK(hipMemcpyAsync(h->d_data, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
-        MHCK(hipStreamSynchronize(h->stream));   // (`buf` is a local)
+        HIPCK(mp_hipMalloc(h->d_data, buf.size()));
+        HIPCK(hipMemcpyAsync(h->d_data, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));   // (`buf` is a local)
         h->fn->bind_data(h->d_data, h->d_data + nd);
         constraint_sites = rsites.data(); constraint_values = rvals.data(); n_constraints = (int32_t)rsites.size();
     }
     mp_fn_consspec cs{};
-    rc = fn_shared_constraints(ns, constraint_sites, constraint_values, n_constraints, cs);
-    if (rc != MP_OK) return rc;
-    rc = h->fn->generate(h.get(), cs, nullptr, nullptr, 0u);
-    if (rc != MP_OK) return rc;
+    MPCK(fn_shared_constraints(ns, constraint_sites, constraint_values, n_constraints, cs));
+    MPCK(h->fn->generate(h.get(), cs, nullptr, nullptr, 0u));
     return mh_finish(h.get(), nullptr);   // a constraint on a site the model never visits is the reference's panic
 }
 int32_t mp_mh_create_fn(int32_t model_kind, const double* params, int32_t n_params, const int32_t* constraint_sites, const double* constraint_values,
@@ -622,11 +611,10 @@ int32_t mp_fn_generate_create(int32_t model_kind, const double* params, int32_t 
     if (!out) return mp_set_error(MP_ERR_INVALID_ARG, "out is null");
     *out = nullptr;
     std::unique_ptr<mp_mh, mh_cleanup> h;
-    int32_t rc = fn_create_generate(model_kind, params, n_params, constraint_sites, constraint_values, n_constraints, n_chains, seed, device, stream, h);
-    if (rc != MP_OK) return rc;
+    MPCK(fn_create_generate(model_kind, params, n_params, constraint_sites, constraint_values, n_constraints, n_chains, seed, device, stream, h));
     if (weights_out) {
-        MHCK(hipMemcpyAsync(weights_out, h->tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-        MHCK(hipStreamSynchronize(h->stream));
+        HIPCK(hipMemcpyAsync(weights_out, h->tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));
     }
     *out = h.release();
     return MP_OK;
@@ -636,13 +624,11 @@ int32_t mp_fn_simulate_create(int32_t model_kind, const double* params, int32_t 
     if (!out) return mp_set_error(MP_ERR_INVALID_ARG, "out is null");
     *out = nullptr;
     std::unique_ptr<mp_mh, mh_cleanup> h;
-    int32_t rc = fn_alloc(model_kind, params, n_params, n_chains, seed, device, stream, h);
-    if (rc != MP_OK) return rc;
+    MPCK(fn_alloc(model_kind, params, n_params, n_chains, seed, device, stream, h));
     if (h->fn->n_data() > 0) return mp_set_error(MP_ERR_UNSUPPORTED, "simulate: the model declares data sites (observed by definition, mp_genfn.h)");
-    rc = h->fn->simulate(h.get(), 0u);
-    if (rc != MP_OK) return rc;
-    if (logjp_out) MHCK(hipMemcpyAsync(logjp_out, h->tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipStreamSynchronize(h->stream));
+    MPCK(h->fn->simulate(h.get(), 0u));
+    if (logjp_out) HIPCK(hipMemcpyAsync(logjp_out, h->tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
     *out = h.release();
     return MP_OK;
 }
@@ -653,10 +639,8 @@ static int32_t fn_importance(int32_t model_kind, const double* params, int32_t n
                              double* log_normalized_weights, uint64_t* resampled_indices, mp_mh** traces_out) {
     if (traces_out) *traces_out = nullptr;
     std::unique_ptr<mp_mh, mh_cleanup> h;
-    int32_t rc = fn_create_generate(model_kind, params, n_params, constraint_sites, constraint_values, n_constraints, num_samples, seed, device, nullptr, h);
-    if (rc != MP_OK) return rc;
-    rc = mp_is_finish_device(h->tmp, h->n, num_ret_samples, seed, device, h->stream, log_ml_estimate, log_normalized_weights, resampled_indices);
-    if (rc != MP_OK) return rc;
+    MPCK(fn_create_generate(model_kind, params, n_params, constraint_sites, constraint_values, n_constraints, num_samples, seed, device, nullptr, h));
+    MPCK(mp_is_finish_device(h->tmp, h->n, num_ret_samples, seed, device, h->stream, log_ml_estimate, log_normalized_weights, resampled_indices));
     if (traces_out) *traces_out = h.release();
     return MP_OK;
 }
@@ -680,13 +664,13 @@ static int fn_words_of(const mp_mh* h) { return fn_words(h->fn->ns()); }
 static int32_t present_to_host(mp_mh* h, const uint32_t* d_present, uint32_t* host_out) {
     const int W = fn_words_of(h);
     if (W == 1) {
-        MHCK(hipMemcpyAsync(host_out, d_present, sizeof(uint32_t) * h->n, hipMemcpyDeviceToHost, h->stream));
-        MHCK(hipStreamSynchronize(h->stream));
+        HIPCK(hipMemcpyAsync(host_out, d_present, sizeof(uint32_t) * h->n, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));
         return MP_OK;
     }
     std::vector<uint32_t> t((size_t)W * h->n);
-    MHCK(hipMemcpyAsync(t.data(), d_present, sizeof(uint32_t) * t.size(), hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipStreamSynchronize(h->stream));
+    HIPCK(hipMemcpyAsync(t.data(), d_present, sizeof(uint32_t) * t.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
     for (u64 i = 0; i < h->n; ++i)
         for (int w = 0; w < W; ++w) host_out[i * (u64)W + w] = t[(size_t)w * h->n + i];
     return MP_OK;
@@ -694,15 +678,15 @@ static int32_t present_to_host(mp_mh* h, const uint32_t* d_present, uint32_t* ho
 static int32_t present_to_device(mp_mh* h, const uint32_t* host_in, uint32_t* d_present) {
     const int W = fn_words_of(h);
     if (W == 1) {
-        MHCK(hipMemcpyAsync(d_present, host_in, sizeof(uint32_t) * h->n, hipMemcpyHostToDevice, h->stream));
-        MHCK(hipStreamSynchronize(h->stream));
+        HIPCK(hipMemcpyAsync(d_present, host_in, sizeof(uint32_t) * h->n, hipMemcpyHostToDevice, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));
         return MP_OK;
     }
     std::vector<uint32_t> t((size_t)W * h->n);
     for (u64 i = 0; i < h->n; ++i)
         for (int w = 0; w < W; ++w) t[(size_t)w * h->n + i] = host_in[i * (u64)W + w];
-    MHCK(hipMemcpyAsync(d_present, t.data(), sizeof(uint32_t) * t.size(), hipMemcpyHostToDevice, h->stream));
-    MHCK(hipStreamSynchronize(h->stream));   // `t` is a local
+    HIPCK(hipMemcpyAsync(d_present, t.data(), sizeof(uint32_t) * t.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));   // `t` is a local
     return MP_OK;
 }
 
@@ -716,11 +700,11 @@ int32_t mp_mh_n_sites(mp_mh* h, int32_t* out) {
 int32_t mp_mh_read_trace(mp_mh* h, double* values, uint32_t* present) {
     if (!h || !values || !present) return mp_set_error(MP_ERR_INVALID_ARG, "null argument");
     if (!h->fn) return mp_set_error(MP_ERR_UNSUPPORTED, "chains of a registered generative function only (mp_mh_create_fn)");
-    MHCK(hipSetDevice(h->device));
+    HIPCK(hipSetDevice(h->device));
     const int ns = h->fn->ns();
     std::vector<double> v((size_t)ns * h->n);
-    MHCK(hipMemcpyAsync(v.data(), h->fvals, sizeof(double) * v.size(), hipMemcpyDeviceToHost, h->stream));
-    { const int32_t rcp = present_to_host(h, h->fpresent, present); if (rcp != MP_OK) return rcp; }   // (waits for the stream)
+    HIPCK(hipMemcpyAsync(v.data(), h->fvals, sizeof(double) * v.size(), hipMemcpyDeviceToHost, h->stream));
+    MPCK(present_to_host(h, h->fpresent, present));   // (waits for the stream)
     for (u64 i = 0; i < h->n; ++i)
         for (int k = 0; k < ns; ++k) values[i * (u64)ns + k] = v[(size_t)k * h->n + i];
     return MP_OK;
@@ -732,13 +716,13 @@ int32_t mp_mh_read_trace(mp_mh* h, double* values, uint32_t* present) {
 int32_t mp_mh_site_moments(mp_mh* h, uint64_t* count_out, double* mean_out, double* var_out) {
     if (!h || !count_out || !mean_out) return mp_set_error(MP_ERR_INVALID_ARG, "null argument");
     if (!h->fn) return mp_set_error(MP_ERR_UNSUPPORTED, "chains of a registered generative function only (mp_mh_create_fn)");
-    MHCK(hipSetDevice(h->device));
+    HIPCK(hipSetDevice(h->device));
     const int ns = h->fn->ns();
     const u64 nb = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);
     if (!h->mom_res) {
-        MHCK(mp_hipMalloc(h->mom_buf[0], 2 * (size_t)ns * nb));
-        MHCK(mp_hipMalloc(h->mom_buf[1], 2 * (size_t)ns * ((nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN)));
-        MHCK(mp_hipMalloc(h->mom_res, 4 * (size_t)ns));
+        HIPCK(mp_hipMalloc(h->mom_buf[0], 2 * (size_t)ns * nb));
+        HIPCK(mp_hipMalloc(h->mom_buf[1], 2 * (size_t)ns * ((nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN)));
+        HIPCK(mp_hipMalloc(h->mom_res, 4 * (size_t)ns));
     }
     double* const buf[2] = {h->mom_buf[0].get(), h->mom_buf[1].get()};
     double* res = h->mom_res;
@@ -751,8 +735,8 @@ int32_t mp_mh_site_moments(mp_mh* h, uint64_t* count_out, double* mean_out, doub
     }
     { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return mp_set_error(MP_ERR_HIP, std::string("mp_mh_site_moments kernels: ") + hipGetErrorString(e)); }
     std::vector<double> r(4 * (size_t)ns);
-    MHCK(hipMemcpyAsync(r.data(), res, sizeof(double) * r.size(), hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipStreamSynchronize(h->stream));
+    HIPCK(hipMemcpyAsync(r.data(), res, sizeof(double) * r.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
     for (int s = 0; s < ns; ++s) {
         const double cnt = r[2 * s + 1];   // a tree of 0.0 / 1.0: exact
         count_out[s] = (uint64_t)cnt;
@@ -766,10 +750,9 @@ int32_t mp_mh_site_moments(mp_mh* h, uint64_t* count_out, double* mean_out, doub
 static int32_t mh_fn_step(mp_mh* h, int32_t proposal_kind, const double* args, int32_t n_args, int32_t n_iters, uint64_t* accepted) {
     if (n_iters < 0) return mp_set_error(MP_ERR_INVALID_ARG, "n_iters < 0");
     if (n_args < 0 || (n_args > 0 && !args)) return mp_set_error(MP_ERR_INVALID_ARG, "bad proposal_args");
-    MHCK(hipSetDevice(h->device));
-    MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
-    const int32_t rc = h->fn->mh(h, proposal_kind, args, n_args, n_iters);
-    if (rc != MP_OK) return rc;
+    HIPCK(hipSetDevice(h->device));
+    HIPCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
+    MPCK(h->fn->mh(h, proposal_kind, args, n_args, n_iters));
     h->iters += (u64)n_iters;
     return mh_finish(h, accepted);
 }
@@ -785,10 +768,9 @@ static int32_t mh_fn_regen(mp_mh* h, const int32_t* mask_sites, int32_t n_mask, 
     m.n_cycle = (cycle && n_mask > 0) ? n_mask : 0;
     if (n_mask == 0 && h->fn->n_data() > 0)
         return mp_set_error(MP_ERR_UNSUPPORTED, "regen_mh with the empty mask re-simulates the whole schema, observed sites included (dyngenfn.rs:571): not for a model with declared data sites");
-    MHCK(hipSetDevice(h->device));
-    MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
-    const int32_t rc = h->fn->regen(h, m, n_iters);
-    if (rc != MP_OK) return rc;
+    HIPCK(hipSetDevice(h->device));
+    HIPCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
+    MPCK(h->fn->regen(h, m, n_iters));
     h->iters += (u64)n_iters;
     return mh_finish(h, accepted);
 }
@@ -813,15 +795,15 @@ int32_t mp_mh_step(mp_mh* h, int32_t proposal_kind, const double* proposal_args,
         N.l00 = L[0]; N.l10 = L[2]; N.l11 = L[3];
         for (int q = 0; q < 4; ++q) N.inv[q] = inv[q];
         N.ln_det = mp_log(mp_host_det(cov, 2));
-        MHCK(hipSetDevice(h->device));
-        MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64), h->stream));
+        HIPCK(hipSetDevice(h->device));
+        HIPCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64), h->stream));
         hipLaunchKernelGGL(k_pointed_iterate, dim3((unsigned)((h->n + MH_THREADS - 1) / MH_THREADS)), dim3(MH_THREADS), 0, h->stream, h->n,
                            (uint32_t)h->seed, (uint32_t)(h->seed >> 32), (uint32_t)(h->iters + 1), n_iters, h->pointed, N, h->lat, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         h->iters += (u64)n_iters;
         if (accepted) {
-            MHCK(hipMemcpyAsync(accepted, h->d_acc, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-            MHCK(hipStreamSynchronize(h->stream));
+            HIPCK(hipMemcpyAsync(accepted, h->d_acc, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+            HIPCK(hipStreamSynchronize(h->stream));
         }
         return MP_OK;
     }
@@ -843,20 +825,20 @@ int32_t mp_regen_mh_step(mp_mh* h, const int32_t* mask_sites, int32_t n_mask, in
     if (n_mask == 0) {
         // empty mask = the trace's whole schema (dyngenfn.rs:571): every site, the observed ones included, is redrawn
         if (n_iters < 0) return mp_set_error(MP_ERR_INVALID_ARG, "n_iters < 0");
-        MHCK(hipSetDevice(h->device));
+        HIPCK(hipSetDevice(h->device));
         const unsigned grid = (unsigned)((h->n + MH_THREADS - 1) / MH_THREADS);
         if (!h->ys_chain) {
-            MHCK(mp_hipMalloc(h->ys_chain, h->n * (size_t)h->data.n));
+            HIPCK(mp_hipMalloc(h->ys_chain, h->n * (size_t)h->data.n));
             hipLaunchKernelGGL(k_mh_broadcast_ys, dim3(grid), dim3(MH_THREADS), 0, h->stream, h->n, h->data, h->ys_chain);
         }
-        MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64), h->stream));
+        HIPCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64), h->stream));
         hipLaunchKernelGGL(k_mh_regenerate_all, dim3(grid), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32),
                            (uint32_t)(h->iters + 1), n_iters, h->data, h->is_lin, h->a, h->b, h->c, h->ys_chain, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         h->iters += (u64)n_iters;
         if (accepted) {
-            MHCK(hipMemcpyAsync(accepted, h->d_acc, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-            MHCK(hipStreamSynchronize(h->stream));
+            HIPCK(hipMemcpyAsync(accepted, h->d_acc, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+            HIPCK(hipStreamSynchronize(h->stream));
         }
         return MP_OK;
     }
@@ -875,48 +857,47 @@ int32_t mp_regen_mh_step(mp_mh* h, const int32_t* mask_sites, int32_t n_mask, in
 int32_t mp_mh_read_state(mp_mh* h, double* out) {
     if (!h || !out) return mp_set_error(MP_ERR_INVALID_ARG, "null argument");
     if (h->fn) return mp_set_error(MP_ERR_UNSUPPORTED, "chains of a registered generative function: mp_mh_read_trace");
-    MHCK(hipSetDevice(h->device));
+    HIPCK(hipSetDevice(h->device));
     if (h->kind == MP_MH_MODEL_POINTED_2D) {
-        MHCK(hipMemcpyAsync(out, h->lat, sizeof(double) * 2 * h->n, hipMemcpyDeviceToHost, h->stream));
-        MHCK(hipStreamSynchronize(h->stream));
+        HIPCK(hipMemcpyAsync(out, h->lat, sizeof(double) * 2 * h->n, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));
         return MP_OK;
     }
     std::vector<int> il(h->n);
     std::vector<double> a(h->n), b(h->n), c(h->n);
-    MHCK(hipMemcpyAsync(il.data(), h->is_lin, sizeof(int) * h->n, hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipMemcpyAsync(a.data(), h->a, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipMemcpyAsync(b.data(), h->b, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipMemcpyAsync(c.data(), h->c, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipStreamSynchronize(h->stream));
+    HIPCK(hipMemcpyAsync(il.data(), h->is_lin, sizeof(int) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipMemcpyAsync(a.data(), h->a, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipMemcpyAsync(b.data(), h->b, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipMemcpyAsync(c.data(), h->c, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
     for (u64 i = 0; i < h->n; ++i) { out[4 * i] = il[i]; out[4 * i + 1] = a[i]; out[4 * i + 2] = b[i]; out[4 * i + 3] = c[i]; }
     return MP_OK;
 }
 
 int32_t mp_mh_read_logjp(mp_mh* h, double* out) {
     if (!h || !out) return mp_set_error(MP_ERR_INVALID_ARG, "null argument");
-    MHCK(hipSetDevice(h->device));
+    HIPCK(hipSetDevice(h->device));
     if (h->fn) {
-        const int32_t rc = h->fn->logjp(h);
-        if (rc != MP_OK) return rc;
+        MPCK(h->fn->logjp(h));
     } else if (h->kind == MP_MH_MODEL_POINTED_2D)
         hipLaunchKernelGGL(k_pointed_logjp, dim3((unsigned)((h->n + MH_THREADS - 1) / MH_THREADS)), dim3(MH_THREADS), 0, h->stream, h->n, h->pointed, h->lat,
                            h->tmp);
     else
     hipLaunchKernelGGL(k_mh_logjp, dim3((unsigned)((h->n + MH_THREADS - 1) / MH_THREADS)), dim3(MH_THREADS), 0, h->stream, h->n, h->data, h->ln_noise,
                        h->is_lin, h->a, h->b, h->c, h->tmp, (const double*)h->ys_chain);
-    MHCK(hipGetLastError());
-    MHCK(hipMemcpyAsync(out, h->tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    MHCK(hipStreamSynchronize(h->stream));
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(out, h->tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
     return MP_OK;
 }
 
 int32_t mp_mh_read_observations(mp_mh* h, double* out) {
     if (!h || !out) return mp_set_error(MP_ERR_INVALID_ARG, "null argument");
     if (h->fn || h->kind != MP_MH_MODEL_HIERARCHICAL) return mp_set_error(MP_ERR_UNSUPPORTED, "the hierarchical model's (y, i) choices (registered functions: mp_mh_read_trace)");
-    MHCK(hipSetDevice(h->device));
+    HIPCK(hipSetDevice(h->device));
     if (h->ys_chain) {
-        MHCK(hipMemcpyAsync(out, h->ys_chain, sizeof(double) * h->n * (size_t)h->data.n, hipMemcpyDeviceToHost, h->stream));
-        MHCK(hipStreamSynchronize(h->stream));
+        HIPCK(hipMemcpyAsync(out, h->ys_chain, sizeof(double) * h->n * (size_t)h->data.n, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));
     } else {
         for (u64 i = 0; i < h->n; ++i)
             for (int k = 0; k < h->data.n; ++k) out[i * (u64)h->data.n + k] = h->data.ys[k];
@@ -936,10 +917,10 @@ static int32_t gfi_scratch(mp_mh* h) {
     if (!h->gfi_vals) {   // all four or none: the handle gets them only when every allocation succeeded
         mp_dev<double> vals, cons;
         mp_dev<uint32_t> present, cpresent;
-        MHCK(mp_hipMalloc(vals, ns * h->n));
-        MHCK(mp_hipMalloc(present, h->n * (size_t)fn_words_of(h)));
-        MHCK(mp_hipMalloc(cons, ns * h->n));
-        MHCK(mp_hipMalloc(cpresent, h->n * (size_t)fn_words_of(h)));
+        HIPCK(mp_hipMalloc(vals, ns * h->n));
+        HIPCK(mp_hipMalloc(present, h->n * (size_t)fn_words_of(h)));
+        HIPCK(mp_hipMalloc(cons, ns * h->n));
+        HIPCK(mp_hipMalloc(cpresent, h->n * (size_t)fn_words_of(h)));
         h->gfi_vals = std::move(vals); h->gfi_present = std::move(present); h->gfi_cons = std::move(cons); h->gfi_cpresent = std::move(cpresent);
     }
     return MP_OK;
@@ -957,8 +938,8 @@ static int32_t gfi_constraints(mp_mh* h, const int32_t* sites, const double* val
             if ((ns & 31) && (top >> (ns & 31))) return mp_set_error(MP_ERR_INVALID_ARG, "chain_present names a site the model does not have");
             for (int k = 0; k < ns; ++k) t[(size_t)k * h->n + i] = chain_values[i * (u64)ns + k];
         }
-        MHCK(hipMemcpyAsync(h->gfi_cons, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, h->stream));
-        { const int32_t rcp = present_to_device(h, chain_present, h->gfi_cpresent); if (rcp != MP_OK) return rcp; }   // (waits for the stream: `t` is a local)
+        HIPCK(hipMemcpyAsync(h->gfi_cons, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, h->stream));
+        MPCK(present_to_device(h, chain_present, h->gfi_cpresent));   // (waits for the stream: `t` is a local)
         out.d_vals = h->gfi_cons;
         out.d_present = h->gfi_cpresent;
         return MP_OK;
@@ -979,25 +960,25 @@ static int32_t gfi_constraints(mp_mh* h, const int32_t* sites, const double* val
 static int32_t gfi_check(mp_mh* h) {
     if (!h) return mp_set_error(MP_ERR_INVALID_ARG, "null handle");
     if (!h->fn) return mp_set_error(MP_ERR_UNSUPPORTED, "chains of a registered generative function only (mp_mh_create_fn)");
-    MHCK(hipSetDevice(h->device));
+    HIPCK(hipSetDevice(h->device));
     return gfi_scratch(h);
 }
 static int32_t gfi_take_step(mp_mh* h, uint32_t rng_step, uint32_t* step) {
-    MHCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
+    HIPCK(hipMemsetAsync(h->d_acc, 0, sizeof(u64) * 2, h->stream));
     *step = rng_step ? rng_step : (uint32_t)(++h->iters);
     return MP_OK;
 }
 static int32_t gfi_weights(mp_mh* h, double* weights_out) {
-    if (weights_out) MHCK(hipMemcpyAsync(weights_out, h->tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+    if (weights_out) HIPCK(hipMemcpyAsync(weights_out, h->tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     return mh_finish(h, nullptr);   // (waits for the stream; chains that reached a case the reference panics on are an error)
 }
 static int32_t gfi_table(mp_mh* h, double* values_out, uint32_t* present_out) {   // the discard / the choices: [site][chain] -> [chain][site]
     if (!values_out && !present_out) return MP_OK;
     const int ns = h->fn->ns();
     std::vector<double> v((size_t)ns * h->n);
-    MHCK(hipMemcpyAsync(v.data(), h->gfi_vals, sizeof(double) * v.size(), hipMemcpyDeviceToHost, h->stream));
-    if (present_out) { const int32_t rcp = present_to_host(h, h->gfi_present, present_out); if (rcp != MP_OK) return rcp; }
-    MHCK(hipStreamSynchronize(h->stream));
+    HIPCK(hipMemcpyAsync(v.data(), h->gfi_vals, sizeof(double) * v.size(), hipMemcpyDeviceToHost, h->stream));
+    if (present_out) MPCK(present_to_host(h, h->gfi_present, present_out));
+    HIPCK(hipStreamSynchronize(h->stream));
     if (values_out)
         for (u64 i = 0; i < h->n; ++i)
             for (int k = 0; k < ns; ++k) values_out[i * (u64)ns + k] = v[(size_t)k * h->n + i];
@@ -1007,26 +988,20 @@ static int32_t gfi_table(mp_mh* h, double* values_out, uint32_t* present_out) { 
 int32_t mp_fn_update(mp_mh* h, int32_t argdiff, uint32_t rng_step, const int32_t* sites, const double* values, int32_t n_constraints,
                      const double* chain_values, const uint32_t* chain_present, double* weights_out, double* discard_values_out,
                      uint32_t* discard_present_out) {
-    int32_t rc = gfi_check(h);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_check(h));
     if (argdiff != MP_ARGDIFF_NOCHANGE && argdiff != MP_ARGDIFF_UNKNOWN) return mp_set_error(MP_ERR_INVALID_ARG, "argdiff: MP_ARGDIFF_NOCHANGE or MP_ARGDIFF_UNKNOWN");
     gfi_cons c;
-    rc = gfi_constraints(h, sites, values, n_constraints, chain_values, chain_present, c);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_constraints(h, sites, values, n_constraints, chain_values, chain_present, c));
     const bool want = discard_values_out || discard_present_out;
     uint32_t step = 0;
-    rc = gfi_take_step(h, rng_step, &step);
-    if (rc != MP_OK) return rc;
-    rc = h->fn->update(h, c.cs, c.d_vals, c.d_present, argdiff == MP_ARGDIFF_UNKNOWN, step, want);
-    if (rc != MP_OK) return rc;
-    rc = gfi_weights(h, weights_out);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_take_step(h, rng_step, &step));
+    MPCK(h->fn->update(h, c.cs, c.d_vals, c.d_present, argdiff == MP_ARGDIFF_UNKNOWN, step, want));
+    MPCK(gfi_weights(h, weights_out));
     return want ? gfi_table(h, discard_values_out, discard_present_out) : MP_OK;
 }
 
 int32_t mp_fn_regenerate(mp_mh* h, int32_t argdiff, uint32_t rng_step, const int32_t* mask_sites, int32_t n_mask, double* weights_out) {
-    int32_t rc = gfi_check(h);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_check(h));
     if (argdiff != MP_ARGDIFF_NOCHANGE && argdiff != MP_ARGDIFF_UNKNOWN) return mp_set_error(MP_ERR_INVALID_ARG, "argdiff: MP_ARGDIFF_NOCHANGE or MP_ARGDIFF_UNKNOWN");
     if (n_mask < 0 || (n_mask > 0 && !mask_sites)) return mp_set_error(MP_ERR_INVALID_ARG, "bad mask");
     uint64_t bits = 0;
@@ -1037,69 +1012,52 @@ int32_t mp_fn_regenerate(mp_mh* h, int32_t argdiff, uint32_t rng_step, const int
     if (n_mask == 0 && h->fn->n_data() > 0)
         return mp_set_error(MP_ERR_UNSUPPORTED, "regenerate with the empty mask re-simulates the whole schema, observed sites included (dyngenfn.rs:571): not for a model with declared data sites");
     uint32_t step = 0;
-    rc = gfi_take_step(h, rng_step, &step);
-    if (rc != MP_OK) return rc;
-    rc = h->fn->regenerate(h, bits, argdiff == MP_ARGDIFF_UNKNOWN, step);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_take_step(h, rng_step, &step));
+    MPCK(h->fn->regenerate(h, bits, argdiff == MP_ARGDIFF_UNKNOWN, step));
     return gfi_weights(h, weights_out);
 }
 
 int32_t mp_fn_assess(mp_mh* h, int32_t proposal_kind, const double* proposal_args, int32_t n_proposal_args, uint32_t rng_step, const int32_t* sites,
                      const double* values, int32_t n_constraints, const double* chain_values, const uint32_t* chain_present, double* weights_out) {
-    int32_t rc = gfi_check(h);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_check(h));
     gfi_cons c;
-    rc = gfi_constraints(h, sites, values, n_constraints, chain_values, chain_present, c);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_constraints(h, sites, values, n_constraints, chain_values, chain_present, c));
     if (proposal_kind >= 0 && (n_proposal_args < 0 || (n_proposal_args > 0 && !proposal_args))) return mp_set_error(MP_ERR_INVALID_ARG, "bad proposal_args");
     uint32_t step = 0;
-    rc = gfi_take_step(h, rng_step, &step);
-    if (rc != MP_OK) return rc;
-    if (proposal_kind < 0) rc = h->fn->assess(h, c.cs, c.d_vals, c.d_present, step);
-    else rc = h->fn->assess_proposal(h, proposal_kind, proposal_args, n_proposal_args, c.cs, c.d_vals, c.d_present, step);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_take_step(h, rng_step, &step));
+    MPCK(proposal_kind < 0 ? h->fn->assess(h, c.cs, c.d_vals, c.d_present, step)
+                           : h->fn->assess_proposal(h, proposal_kind, proposal_args, n_proposal_args, c.cs, c.d_vals, c.d_present, step));
     return gfi_weights(h, weights_out);
 }
 
 int32_t mp_fn_propose(mp_mh* h, int32_t proposal_kind, const double* proposal_args, int32_t n_proposal_args, uint32_t rng_step,
                       double* choice_values_out, uint32_t* choice_present_out, double* weights_out) {
-    int32_t rc = gfi_check(h);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_check(h));
     if (n_proposal_args < 0 || (n_proposal_args > 0 && !proposal_args)) return mp_set_error(MP_ERR_INVALID_ARG, "bad proposal_args");
     uint32_t step = 0;
-    rc = gfi_take_step(h, rng_step, &step);
-    if (rc != MP_OK) return rc;
-    rc = h->fn->propose(h, proposal_kind, proposal_args, n_proposal_args, step);
-    if (rc != MP_OK) return rc;
-    rc = gfi_weights(h, weights_out);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_take_step(h, rng_step, &step));
+    MPCK(h->fn->propose(h, proposal_kind, proposal_args, n_proposal_args, step));
+    MPCK(gfi_weights(h, weights_out));
     return gfi_table(h, choice_values_out, choice_present_out);
 }
 
 int32_t mp_fn_generate(mp_mh* h, uint32_t rng_step, const int32_t* sites, const double* values, int32_t n_constraints, const double* chain_values,
                        const uint32_t* chain_present, double* weights_out) {
-    int32_t rc = gfi_check(h);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_check(h));
     gfi_cons c;
-    rc = gfi_constraints(h, sites, values, n_constraints, chain_values, chain_present, c);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_constraints(h, sites, values, n_constraints, chain_values, chain_present, c));
     uint32_t step = 0;
-    rc = gfi_take_step(h, rng_step, &step);
-    if (rc != MP_OK) return rc;
-    rc = h->fn->generate(h, c.cs, c.d_vals, c.d_present, step);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_take_step(h, rng_step, &step));
+    MPCK(h->fn->generate(h, c.cs, c.d_vals, c.d_present, step));
     return gfi_weights(h, weights_out);
 }
 
 int32_t mp_fn_simulate(mp_mh* h, uint32_t rng_step, double* logjp_out) {
-    int32_t rc = gfi_check(h);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_check(h));
     if (h->fn->n_data() > 0) return mp_set_error(MP_ERR_UNSUPPORTED, "simulate: the model declares data sites (observed by definition, mp_genfn.h)");
     uint32_t step = 0;
-    rc = gfi_take_step(h, rng_step, &step);
-    if (rc != MP_OK) return rc;
-    rc = h->fn->simulate(h, step);
-    if (rc != MP_OK) return rc;
+    MPCK(gfi_take_step(h, rng_step, &step));
+    MPCK(h->fn->simulate(h, step));
     return gfi_weights(h, logjp_out);
 }
 

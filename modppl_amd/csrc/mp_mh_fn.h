@@ -16,6 +16,7 @@
 #include <functional>
 #include <map>
 
+#include "mp_err.h"
 #include "mp_genfn.h"
 
 struct mp_fn_maskspec {
@@ -386,7 +387,7 @@ struct mh_fn_ops_t : mh_fn_ops {
     int32_t regen(mp_mh* h, const mp_fn_maskspec& m, int n_iters) override {
         hipLaunchKernelGGL(k_fn_regen<M>, dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32),
                            (uint32_t)(h->iters + 1), n_iters, model, m, h->fvals, h->fpresent, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     }
     int32_t mh(mp_mh* h, int proposal_kind, const double* args, int n_args, int n_iters) override {
@@ -399,31 +400,31 @@ struct mh_fn_ops_t : mh_fn_ops {
         hipLaunchKernelGGL(k_fn_update<M>, dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), step, model, cs,
                            d_cvals, d_cpresent, unknown, h->fvals, h->fpresent, h->tmp, want_discard ? h->gfi_vals : (double*)nullptr,
                            want_discard ? h->gfi_present : (uint32_t*)nullptr, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     }
     int32_t regenerate(mp_mh* h, uint64_t mask, int unknown, uint32_t step) override {
         hipLaunchKernelGGL(k_fn_regenerate<M>, dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), step, model,
                            mask, unknown, h->fvals, h->fpresent, h->tmp, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     }
     int32_t assess(mp_mh* h, const mp_fn_consspec& cs, const double* d_cvals, const uint32_t* d_cpresent, uint32_t step) override {
         hipLaunchKernelGGL(k_fn_assess<M>, dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), step, model, cs,
                            d_cvals, d_cpresent, h->tmp, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     }
     int32_t generate(mp_mh* h, const mp_fn_consspec& cs, const double* d_cvals, const uint32_t* d_cpresent, uint32_t step) override {
         hipLaunchKernelGGL(k_fn_generate<M>, dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), step, model, cs,
                            d_cvals, d_cpresent, h->fvals, h->fpresent, h->tmp, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     }
     int32_t simulate(mp_mh* h, uint32_t step) override {
         hipLaunchKernelGGL(k_fn_simulate<M>, dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), step, model,
                            h->fvals, h->fpresent, h->tmp);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     }
     int32_t propose(mp_mh* h, int proposal_kind, const double* args, int n_args, uint32_t step) override {
@@ -442,7 +443,7 @@ struct mh_fn_ops_t : mh_fn_ops {
     int32_t logjp(mp_mh* h) override {
         hipLaunchKernelGGL(k_fn_logjp<M>, dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, model, (const double*)h->fvals,
                            (const uint32_t*)h->fpresent, h->tmp);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     }
 };
@@ -472,7 +473,7 @@ static int mp_mh_register_proposal(int kind, bool (*parse)(const double*, int, P
         if (!parse(args, n_args, prop, err)) return mp_set_error(MP_ERR_INVALID_ARG, err);
         hipLaunchKernelGGL((k_fn_mh<M, P>), dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32),
                            (uint32_t)(h->iters + 1), n_iters, model, prop, h->fvals, h->fpresent, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     };
     L.propose = [parse](mp_mh* h, const M& model, const double* args, int n_args, uint32_t step) -> int32_t {
@@ -481,7 +482,7 @@ static int mp_mh_register_proposal(int kind, bool (*parse)(const double*, int, P
         if (!parse(args, n_args, prop, err)) return mp_set_error(MP_ERR_INVALID_ARG, err);
         hipLaunchKernelGGL((k_fn_propose<M, P>), dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), step,
                            model, prop, (const double*)h->fvals, (const uint32_t*)h->fpresent, h->tmp, h->gfi_vals, h->gfi_present);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     };
     L.assess = [parse](mp_mh* h, const M& model, const double* args, int n_args, const mp_fn_consspec& cs, const double* d_cvals,
@@ -491,7 +492,7 @@ static int mp_mh_register_proposal(int kind, bool (*parse)(const double*, int, P
         if (!parse(args, n_args, prop, err)) return mp_set_error(MP_ERR_INVALID_ARG, err);
         hipLaunchKernelGGL((k_fn_assess_proposal<M, P>), dim3(fn_grid(h)), dim3(MH_THREADS), 0, h->stream, h->n, (uint32_t)h->seed, (uint32_t)(h->seed >> 32),
                            step, model, prop, cs, d_cvals, d_cpresent, (const double*)h->fvals, (const uint32_t*)h->fpresent, h->tmp, h->d_acc);
-        MHCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MP_OK;
     };
     mh_fn_proposals<M>()[kind] = L;

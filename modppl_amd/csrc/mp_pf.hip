@@ -37,11 +37,13 @@
 #include <cstdlib>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/modppl_hip.h"
 #include "mp_diag.h"
+#include "mp_err.h"
 #include "mp_hip_own.h"
 #include "mp_linalg.h"
 // models register themselves (mp_models.h, MP_REGISTER_UNFOLD_MODEL): here a registration creates the device factory
@@ -56,18 +58,12 @@ typedef unsigned long long u64;
 // ---------------------------------------------------------------------------------------------
 // error plumbing
 // ---------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
+static thread_local std::string g_err;   // what mp_last_error() returns; HIPCK, MPCK and the shared checks: mp_err.h
 static int32_t mp_fail(int32_t code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-int32_t mp_set_error(int32_t code, const std::string& msg) { return mp_fail(code, msg); }  // shared with mp_mh.hip
-#define HIPCK(call)                                                                                  \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess)                                                                        \
-            return mp_fail(MP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));           \
-    } while (0)
+int32_t mp_set_error(int32_t code, const std::string& msg) { return mp_fail(code, msg); }  // every other translation unit's way in
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes for mp_shard_native.h (resolved with dlsym at first use: no link-time dependency)
@@ -140,22 +136,29 @@ struct ModelOps {
     int dim_state = 0, dim_obs = 0;
     mp_dev<double> owned_device_mem;    // model constants that do not fit kernel arguments (freed with the model)
     int max_normals = 0;
+    bool light = false;      // k1_light<Model>(): its k_propagate is the 1024-thread kernel
     bool can_draw = false;   // its k_propagate can make the previous resample's draws itself (lanes of two adjacent slots: the 1024-thread launch shape)
     virtual ~ModelOps() = default;
     virtual int propagate(const PropagateArgs& a) const = 0;   // -> MP_K1_FORM_* of the kernel it launched
     virtual int n_normals(long long t) const = 0;
     virtual void simulate(u64 n, uint32_t k0, uint32_t k1, int n_steps, const mp_state0& s0, double* states, double* obs, hipStream_t st) const = 0;
 };
+// light kernels (few registers) run 1024 threads x 2 particles per tile: twice the waves in flight for the same 2048-slot tile.  The
+// launch shape, can_draw and launch_propagate's walk rule (ModelOps::light) all come from this one trait.
+template <class Model>
+constexpr bool k1_light() { return Model::MAX_NORMALS <= 4 && Model::DIM_STATE <= 4; }
+
 template <class Model>
 struct ModelOpsT : ModelOps {
+    static constexpr int THREADS = k1_light<Model>() ? 1024 : TILE_THREADS;
     Model model;
     explicit ModelOpsT(const Model& m) : model(m) {
         dim_state = Model::DIM_STATE;
         dim_obs = Model::DIM_OBS;
         max_normals = Model::MAX_NORMALS;
-        // (the conditions of CAN_DRAW in k_propagate, for the launch configuration `propagate` below picks)
-        can_draw = Model::MAX_NORMALS <= 4 && Model::DIM_STATE <= 4 &&   // = the 1024-thread, two-slot-lane launch shape of `propagate` below
-                   !std::is_same<Model, mp_lgssm_dense<16>>::value && k1_threads_override() == 0;   // (that override launches other lane shapes)
+        light = k1_light<Model>();
+        // (the conditions of CAN_DRAW in k_propagate, for the launch configuration `propagate` below picks: the 1024-thread, two-slot-lane shape)
+        can_draw = light && !std::is_same<Model, mp_lgssm_dense<16>>::value && k1_threads_override() == 0;   // (that override launches other lane shapes)
         static_assert(Model::DIM_STATE <= MP_MAX_STATE && Model::DIM_OBS <= MP_MAX_OBS, "model too wide for mp_obs / mp_state0");
         static_assert(TILE_ITEMS % k1_items<Model>() == 0, "rounds of k_propagate");
     }
@@ -163,24 +166,10 @@ struct ModelOpsT : ModelOps {
         hipLaunchKernelGGL(k_simulate<Model>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, model, n, k0, k1, n_steps, s0, states, obs);
     }
     int propagate(const PropagateArgs& a) const override {
-        // light kernels (few registers) run 1024 threads x 2 particles per tile: twice the waves in flight for the same 2048-slot tile
-        constexpr int THREADS = (Model::MAX_NORMALS <= 4 && Model::DIM_STATE <= 4) ? 1024 : TILE_THREADS;
         const int k1t = k1_threads_override();   // A/B measurements
         if constexpr (std::is_same<Model, mp_lgssm1>::value) {
-            if (k1t == 256) {
-                hipLaunchKernelGGL((k_propagate<Model, 256>), dim3(a.grid), dim3(256), a.dyn_lds, a.stream, a.drw_v.tile_m_old, a.drw_v.tile_W_old, a.drw_v.tile_W2_old,
-                                   a.drw_v.nt, a.drw, model, a.n, a.slot_offset, a.k0, a.k1, a.t,
-                                   a.x_in, a.x_out, a.logw, a.obs, a.s0, a.overwrite, a.dfr_row, a.inv_rows, a.cx_old, a.tail,
-                                   a.inv, a.dfr_lt, a.aux, a.drw_v, a.rc);
-                return MP_K1_FORM_TILE;
-            }
-            if (k1t == 512) {
-                hipLaunchKernelGGL((k_propagate<Model, 512>), dim3(a.grid), dim3(512), a.dyn_lds, a.stream, a.drw_v.tile_m_old, a.drw_v.tile_W_old, a.drw_v.tile_W2_old,
-                                   a.drw_v.nt, a.drw, model, a.n, a.slot_offset, a.k0, a.k1, a.t,
-                                   a.x_in, a.x_out, a.logw, a.obs, a.s0, a.overwrite, a.dfr_row, a.inv_rows, a.cx_old, a.tail,
-                                   a.inv, a.dfr_lt, a.aux, a.drw_v, a.rc);
-                return MP_K1_FORM_TILE;
-            }
+            if (k1t == 256) return k1<256>(a);
+            if (k1t == 512) return k1<512>(a);
         }
         if constexpr (std::is_same<Model, mp_lgssm_dense<16>>::value) {
             // the dense transition's products on the matrix cores (k_propagate_dense16); MP_DENSE_MFMA=0 keeps the scalar
@@ -225,187 +214,58 @@ struct ModelOpsT : ModelOps {
         const bool lat = a.drw && (sch == 1 || sch == 2);
         const bool tab2 = a.drw && !shd && a.drw_v.nt > THREADS;
         if constexpr (THREADS == 1024) {
-            if (shd) return lat ? (a.walk_bisect ? k1<false, true, true, true>(a) : k1<false, true, true, false>(a))
-                                : (a.walk_bisect ? k1<false, false, true, true>(a) : k1<false, false, true, false>(a));
-            if (tab2) return lat ? k1<true, true, false, false>(a) : k1<true, false, false, false>(a);
-            if (lat) return a.walk_bisect ? k1<false, true, false, true>(a) : k1<false, true, false, false>(a);
+            if (shd) return lat ? (a.walk_bisect ? k1<THREADS, false, true, true, true>(a) : k1<THREADS, false, true, true, false>(a))
+                                : (a.walk_bisect ? k1<THREADS, false, false, true, true>(a) : k1<THREADS, false, false, true, false>(a));
+            if (tab2) return lat ? k1<THREADS, true, true, false, false>(a) : k1<THREADS, true, false, false, false>(a);
+            if (lat) return a.walk_bisect ? k1<THREADS, false, true, false, true>(a) : k1<THREADS, false, true, false, false>(a);
         }
-        return a.walk_bisect ? k1<false, false, false, true>(a) : k1<false, false, false, false>(a);
+        return a.walk_bisect ? k1<THREADS, false, false, false, true>(a) : k1<THREADS, false, false, false, false>(a);
     }
-    template <bool TAB2, bool LAT, bool SHD, bool WALKB>
+    int n_normals(long long t) const override { return model.n_normals(t); }
+
+private:
+    // the one place k_propagate's argument list is written out
+    template <int T, bool TAB2 = false, bool LAT = false, bool SHD = false, bool WALKB = false>
     int k1(const PropagateArgs& a) const {
-        constexpr int THREADS = (Model::MAX_NORMALS <= 4 && Model::DIM_STATE <= 4) ? 1024 : TILE_THREADS;
-        hipLaunchKernelGGL((k_propagate<Model, THREADS, TAB2, LAT, SHD, WALKB>), dim3(a.grid), dim3(THREADS), a.dyn_lds, a.stream, a.drw_v.tile_m_old,
+        hipLaunchKernelGGL((k_propagate<Model, T, TAB2, LAT, SHD, WALKB>), dim3(a.grid), dim3(T), a.dyn_lds, a.stream, a.drw_v.tile_m_old,
                            a.drw_v.tile_W_old, a.drw_v.tile_W2_old, a.drw_v.nt, a.drw, model, a.n, a.slot_offset, a.k0, a.k1, a.t,
                            a.x_in, a.x_out, a.logw, a.obs, a.s0, a.overwrite, a.dfr_row, a.inv_rows, a.cx_old, a.tail,
                            a.inv, a.dfr_lt, a.aux, a.drw_v, a.rc);
         return MP_K1_FORM_TILE;
     }
-    int n_normals(long long t) const override { return model.n_normals(t); }
 };
 
-// kind -> factory of the registered models
+// kind -> factory of every model: the built-in ones (mp_models_builtin.h) and those of MP_REGISTER_UNFOLD_MODEL alike
 #include <atomic>
 #include <functional>
 #include <map>
-static std::map<int, std::function<int32_t(const mp_model_desc*, std::unique_ptr<ModelOps>&)>>& model_registry() {
-    static std::map<int, std::function<int32_t(const mp_model_desc*, std::unique_ptr<ModelOps>&)>> r;
+typedef std::function<int32_t(const mp_model_desc*, std::unique_ptr<ModelOps>&)> ModelFactory;
+static std::map<int, ModelFactory>& model_registry() {
+    static std::map<int, ModelFactory> r;
     return r;
+}
+static int mp_register_model_factory(int kind, ModelFactory f) {
+    model_registry()[kind] = std::move(f);
+    return kind;
 }
 template <class M>
 int mp_register_model_hip(int kind, bool (*parse)(const mp_model_desc&, M&, std::string&)) {
-    model_registry()[kind] = [parse](const mp_model_desc* m, std::unique_ptr<ModelOps>& out) -> int32_t {
+    return mp_register_model_factory(kind, [parse](const mp_model_desc* m, std::unique_ptr<ModelOps>& out) -> int32_t {
         M k{};
         std::string err;
         if (!parse(*m, k, err)) return mp_fail(MP_ERR_INVALID_ARG, err);
         out.reset(new ModelOpsT<M>(k));   // instantiates k_propagate / k_simulate / the resample kernels for M
         return MP_OK;
-    };
-    return kind;
+    });
 }
+#include "mp_models_builtin.h"
 
+// (one lookup per handle or one-shot call, never per step)
 static int32_t make_model(const mp_model_desc* m, std::unique_ptr<ModelOps>& out) {
     if (!m) return mp_fail(MP_ERR_INVALID_ARG, "model descriptor is null");
-    switch (m->kind) {
-    case MP_MODEL_LGSSM1: {
-        if (m->n_params != 5 || !m->params) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM1 takes 5 params {mu0,sig0,a,sig_x,sig_y}");
-        if (m->dim_state != 1 || m->dim_obs != 1) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM1: dim_state = dim_obs = 1");
-        mp_lgssm1 k{m->params[0], m->params[1], m->params[2], m->params[3], m->params[4], 0.};
-        if (!(k.sig0 > 0.) || !(k.sig_x > 0.) || !(k.sig_y > 0.)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM1: standard deviations must be > 0");
-        k.ln_sig_y = mp_log(k.sig_y);
-        out.reset(new ModelOpsT<mp_lgssm1>(k));
-        return MP_OK;
-    }
-    case MP_MODEL_SPIRAL: {
-        if (m->dim_state != 2 || m->dim_obs != 2) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_SPIRAL: dim_state = dim_obs = 2");
-        mp_spiral k;
-        const std::vector<double> cov = {0.001, 0., 0., 0.001};  // unfold.rs:29
-        std::vector<double> inv;
-        if (!mp_host_inverse(cov, 2, inv)) return mp_fail(MP_ERR_INVALID_ARG, "covariance not invertible");
-        for (int i = 0; i < 4; ++i) k.cov_inv[i] = inv[i];
-        k.ln_det = mp_log(mp_host_det(cov, 2));
-        std::vector<double> L;
-        if (!mp_host_cholesky(cov, 2, L)) return mp_fail(MP_ERR_INVALID_ARG, "covariance not positive definite");
-        for (int i = 0; i < 4; ++i) { k.chol[i] = L[i]; k.cov[i] = cov[i]; }
-        out.reset(new ModelOpsT<mp_spiral>(k));
-        return MP_OK;
-    }
-    case MP_MODEL_HMM: {
-        if (m->n_params < 2 || !m->params) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_HMM: params = {S, O, prior[S], emission[O][S], transition[S][S]}");
-        const int S = (int)m->params[0], O = (int)m->params[1];
-        if (S < 1 || O < 1 || S > MP_HMM_MAX || O > MP_HMM_MAX) return mp_fail(MP_ERR_UNSUPPORTED, "MP_MODEL_HMM: 1..8 states / observations");
-        if (m->n_params != 2 + S + O * S + S * S) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_HMM: params length mismatch");
-        if (m->dim_state != 1 || m->dim_obs != 1) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_HMM: dim_state = dim_obs = 1");
-        mp_hmm k{};
-        k.n_states = S; k.n_obs = O;
-        const double* prior = m->params + 2;
-        const double* emis = prior + S;
-        const double* trans = emis + O * S;
-        auto sums_to_one = [](const double* p, int n, int stride) {  // categorical.rs:13,23: assert |sum - 1| <= 1e-8
-            double s_ = 0.;
-            for (int i = 0; i < n; ++i) s_ += p[i * stride];
-            return std::fabs(s_ - 1.0) <= 1e-8;
-        };
-        if (!sums_to_one(prior, S, 1)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_HMM: prior does not sum to 1 (eps 1e-8)");
-        for (int s_ = 0; s_ < S; ++s_) {
-            if (!sums_to_one(emis + s_, O, S)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_HMM: emission column does not sum to 1");
-            if (!sums_to_one(trans + s_, S, S)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_HMM: transition column does not sum to 1");
-        }
-        for (int s_ = 0; s_ < S; ++s_) k.prior[s_] = prior[s_];
-        for (int s_ = 0; s_ < S; ++s_) {
-            for (int o = 0; o < O; ++o) k.emission_col[s_][o] = emis[o * S + s_];
-            for (int s2 = 0; s2 < S; ++s2) k.transition_col[s_][s2] = trans[s2 * S + s_];
-        }
-        out.reset(new ModelOpsT<mp_hmm>(k));
-        return MP_OK;
-    }
-    case MP_MODEL_BEARINGS: {
-        if (m->n_params != 6 || !m->params) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_BEARINGS takes 6 params {p0x,p0y,sig_p0,sig_v0,sig_a,sig_theta}");
-        if (m->dim_state != 4 || m->dim_obs != 1) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_BEARINGS: dim_state = 4, dim_obs = 1");
-        mp_bearings k{m->params[0], m->params[1], m->params[2], m->params[3], m->params[4], m->params[5], 0.};
-        if (!(k.sig_p0 > 0.) || !(k.sig_v0 > 0.) || !(k.sig_a > 0.) || !(k.sig_theta > 0.)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_BEARINGS: standard deviations must be > 0");
-        k.ln_sig_theta = mp_log(k.sig_theta);
-        out.reset(new ModelOpsT<mp_bearings>(k));
-        return MP_OK;
-    }
-    case MP_MODEL_LGSSM_BAND: {
-        if (m->n_params != 6 || !m->params) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM_BAND takes 6 params {D,a,band,sig0,sig_x,sig_y}");
-        const int D = (int)m->params[0];
-        if (m->dim_state != D || m->dim_obs != D) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM_BAND: dim_state = dim_obs = D");
-        if (!(m->params[3] > 0.) || !(m->params[4] > 0.) || !(m->params[5] > 0.)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM_BAND: standard deviations must be > 0");
-        const double ln_sy = mp_log(m->params[5]);
-        if (D == 16) { out.reset(new ModelOpsT<mp_lgssm_band<16>>(mp_lgssm_band<16>{m->params[1], m->params[2], m->params[3], m->params[4], m->params[5], ln_sy})); return MP_OK; }
-        if (D == 4) { out.reset(new ModelOpsT<mp_lgssm_band<4>>(mp_lgssm_band<4>{m->params[1], m->params[2], m->params[3], m->params[4], m->params[5], ln_sy})); return MP_OK; }
-        if (D == 2) { out.reset(new ModelOpsT<mp_lgssm_band<2>>(mp_lgssm_band<2>{m->params[1], m->params[2], m->params[3], m->params[4], m->params[5], ln_sy})); return MP_OK; }
-        return mp_fail(MP_ERR_UNSUPPORTED, "MP_MODEL_LGSSM_BAND: D in {2, 4, 16} is compiled in");
-    }
-    case MP_MODEL_POINTED_2D: {
-        if (m->n_params != 8 || !m->params) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_POINTED_2D takes 8 params {xmin,xmax,ymin,ymax, cov row-major}");
-        if (m->dim_state != 2 || m->dim_obs != 2) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_POINTED_2D: dim_state = dim_obs = 2");
-        if (!(m->params[1] > m->params[0]) || !(m->params[3] > m->params[2])) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_POINTED_2D: xmax > xmin and ymax > ymin");
-        mp_pointed2d k{};
-        k.xmin = m->params[0]; k.xmax = m->params[1]; k.ymin = m->params[2]; k.ymax = m->params[3];
-        const std::vector<double> cov(m->params + 4, m->params + 8);
-        std::vector<double> inv;
-        const double det = mp_host_det(cov, 2);
-        if (!(det > 0.) || !mp_host_inverse(cov, 2, inv)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_POINTED_2D: covariance must be invertible with a positive determinant");
-        for (int i = 0; i < 4; ++i) k.cov_inv[i] = inv[i];
-        k.ln_det = mp_log(det);
-        std::vector<double> L;
-        if (!mp_host_cholesky(cov, 2, L)) return mp_fail(MP_ERR_UNSUPPORTED, "MP_MODEL_POINTED_2D: covariance without a Cholesky factor (the reference's eigen fallback is not built)");
-        for (int i = 0; i < 4; ++i) k.chol[i] = L[i];
-        out.reset(new ModelOpsT<mp_pointed2d>(k));
-        return MP_OK;
-    }
-    case MP_MODEL_LINE: {
-        if (m->n_params != 11 || !m->params || m->dim_obs != 11 || m->dim_state != 2)
-            return mp_fail(MP_ERR_UNSUPPORTED, "MP_MODEL_LINE: the 11-point design of tests/importance.rs:62 is compiled in (params = xs[11], dim_state = 2, dim_obs = 11)");
-        mp_line<11> k{};
-        for (int i = 0; i < 11; ++i) k.xs[i] = m->params[i];
-        k.ln_noise = mp_log(0.1);
-        out.reset(new ModelOpsT<mp_line<11>>(k));
-        return MP_OK;
-    }
-    case MP_MODEL_LGSSM_DENSE: {
-        if (!m->params || m->n_params < 2) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM_DENSE: params = {D, sig0, A[D*D], Q[D*D], R[D*D]}");
-        const int D = (int)m->params[0];
-        if (D != 16) return mp_fail(MP_ERR_UNSUPPORTED, "MP_MODEL_LGSSM_DENSE: D = 16 is compiled in (one matrix-core tile)");
-        if (m->n_params != 2 + 3 * D * D || m->dim_state != D || m->dim_obs != D)
-            return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM_DENSE: n_params = 2 + 3 D^2, dim_state = dim_obs = D");
-        const double sig0 = m->params[1];
-        if (!(sig0 > 0.)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM_DENSE: sig0 must be > 0");
-        const double* q = m->params + 2;
-        const std::vector<double> A(q, q + D * D), Q(q + D * D, q + 2 * D * D), R(q + 2 * D * D, q + 3 * D * D);
-        // the per-call nalgebra work of mvnormal.rs:17-18,27-33, once: transform of Q / sig0^2 I / R, inverse and ln det of R
-        std::vector<double> cov0((size_t)D * D, 0.), TQ, T0, TR, Rinv;
-        for (int i = 0; i < D; ++i) cov0[i * D + i] = sig0 * sig0;
-        mp_host_mvnormal_transform(Q, D, TQ);
-        mp_host_mvnormal_transform(cov0, D, T0);
-        mp_host_mvnormal_transform(R, D, TR);
-        const double detR = mp_host_det(R, D);
-        if (!mp_host_inverse(R, D, Rinv)) return mp_fail(MP_ERR_INVALID_ARG, "MP_MODEL_LGSSM_DENSE: R is not invertible (try_inverse().unwrap() panics, mvnormal.rs:18)");
-        std::vector<double> mats;
-        mats.insert(mats.end(), A.begin(), A.end());
-        mats.insert(mats.end(), TQ.begin(), TQ.end());
-        mats.insert(mats.end(), T0.begin(), T0.end());
-        mats.insert(mats.end(), Rinv.begin(), Rinv.end());
-        mats.insert(mats.end(), TR.begin(), TR.end());
-        mp_dev<double> d_mats;
-        HIPCK(mp_hipMalloc(d_mats, mats.size()));
-        if (hipMemcpy(d_mats, mats.data(), sizeof(double) * mats.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return mp_fail(MP_ERR_HIP, "MP_MODEL_LGSSM_DENSE: copying the model matrices failed");
-        mp_lgssm_dense<16> k{d_mats, mp_log(detR)};
-        auto* ops = new ModelOpsT<mp_lgssm_dense<16>>(k);
-        ops->owned_device_mem = std::move(d_mats);
-        out.reset(ops);
-        return MP_OK;
-    }
-    default: {
-        auto it = model_registry().find(m->kind);   // models added through MP_REGISTER_UNFOLD_MODEL (mp_models_extra.h)
-        if (it != model_registry().end()) return it->second(m, out);
-        return mp_fail(MP_ERR_UNSUPPORTED, "model kind " + std::to_string(m->kind) + " is not compiled into this library");
-    }
-    }
+    auto it = model_registry().find(m->kind);
+    if (it != model_registry().end()) return it->second(m, out);
+    return mp_fail(MP_ERR_UNSUPPORTED, "model kind " + std::to_string(m->kind) + " is not compiled into this library");
 }
 
 struct TimedLaunch {
@@ -578,6 +438,22 @@ struct mp_pf {
     uint64_t fam_launches[MP_K_COUNT] = {0, 0, 0, 0};
 };
 
+// the `world` / `rank` arguments of a sharded entry point, and that the handle is one of `world` equal shards
+static int32_t check_world_rank(int32_t world, int32_t rank) {
+    if (world < 1 || world > SH_MAX_WORLD || rank < 0 || rank >= world) return mp_fail(MP_ERR_INVALID_ARG, "1 <= world <= 64, 0 <= rank < world");
+    return MP_OK;
+}
+static int32_t check_world(const mp_pf* h, int32_t world, int32_t rank) {
+    MPCK(check_world_rank(world, rank));
+    if ((u64)world * h->n != h->n_global) return mp_fail(MP_ERR_INVALID_ARG, "equal tile-aligned shards: world * n_particles must equal n_global");
+    return MP_OK;
+}
+
+// the three tile-scalar views of a packed [3][nt] buffer: m (f64 bits), W, W2 — the unit the shards all-gather
+static std::tuple<double*, u64*, u64*> tile_views(u64* base, int nt) {
+    return {reinterpret_cast<double*>(base), base + nt, base + 2 * (size_t)nt};
+}
+
 static mp_tab tab_of(const mp_pf* h) {
     mp_tab t;
     const bool on = h->use_k1_table && !h->sharded && h->tab_ticket && !h->local_table;
@@ -599,9 +475,8 @@ static int32_t update_k1_tail(mp_pf* h) {   // after anything that changes one o
     if (h->cx_alt) {
         t.cx = h->cx_alt;
         t.guide = h->guide_alt;
-        if (h->local_table) {   // (the launch that draws reads the old generation's tile scalars while it writes the new one's)
-            t.tile_m = reinterpret_cast<double*>(h->tiles_alt.get()); t.tile_W = h->tiles_alt + h->nt; t.tile_W2 = h->tiles_alt + 2 * (size_t)h->nt;
-        }
+        // (the launch that draws reads the old generation's tile scalars while it writes the new one's)
+        if (h->local_table) std::tie(t.tile_m, t.tile_W, t.tile_W2) = tile_views(h->tiles_alt, h->nt);
         if (!h->k1_tail_alt) HIPCK(mp_hipMalloc(h->k1_tail_alt, 1));
         HIPCK(hipMemcpyAsync(h->k1_tail_alt, &t, sizeof(t), hipMemcpyHostToDevice, h->stream));
         HIPCK(hipStreamSynchronize(h->stream));
@@ -682,8 +557,7 @@ static int32_t wait_seq(mp_pf* h, const volatile unsigned long long* word, unsig
         }
     }
     std::atomic_thread_fence(std::memory_order_acquire);
-    if (*(volatile int*)h->h_flag)
-        return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+    if (*(volatile int*)h->h_flag) return mp_fail_degenerate();
     return MP_OK;
 }
 static int32_t flush_draws(mp_pf* h);
@@ -698,13 +572,11 @@ static int32_t ensure_lazy(mp_pf* h) {
 }
 static int32_t fetch_scalars(mp_pf* h) {
     {   // (the scalars of a resample are folded by whoever makes its draws)
-        int32_t rcf = flush_draws(h);
-        if (rcf != MP_OK) return rcf;
+        MPCK(flush_draws(h));
     }
     HIPCK(hipMemcpyAsync(h->h_scal, h->scal, sizeof(mp_dev_scalars), hipMemcpyDeviceToHost, h->stream));
     HIPCK(stream_wait(h->stream));
-    if (h->h_scal->degenerate)
-        return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+    if (h->h_scal->degenerate) return mp_fail_degenerate();
     return MP_OK;
 }
 
@@ -724,18 +596,14 @@ static int32_t materialize(mp_pf* h) {
         h->sh_lazy = false;
         h->sh_parents_lazy = false;
         h->x_in_rows = false;   // (every slot's state was just written)
-        int32_t rc = check_launch("k_shard_adopt_rows");
-        if (rc != MP_OK) return rc;
+        MPCK(check_launch("k_shard_adopt_rows"));
     }
     if (h->logw_zero) {
         HIPCK(hipMemsetAsync(h->logw, 0, sizeof(double) * h->n, h->stream));
         h->logw_zero = false;
     }
     if (h->deferred) {
-        {
-            int32_t rcf = flush_draws(h);
-            if (rcf != MP_OK) return rcf;
-        }
+        MPCK(flush_draws(h));
         const int d = h->ops->dim_state;
         hipLaunchKernelGGL(k_resolve_slots<true>, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->n, d, (const u64*)h->dfr_lt,
                            (const uint32_t*)h->dfr_row, (const mp_cx*)h->cx, (const double*)h->x[h->cur], d == 1 ? h->x[h->cur] : h->x[h->cur ^ 1],
@@ -770,7 +638,7 @@ static int32_t hist_alloc(mp_pf* h, size_t bytes, void** out) {
 
 static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs, bool overwrite) {
     // (still pending here = no resample since: this is a further step of the same generation, which accumulates onto the log-weights)
-    { int32_t rcl = ensure_lazy(h); if (rcl != MP_OK) return rcl; }
+    MPCK(ensure_lazy(h));
     PropagateArgs a;
     a.n = h->n; a.slot_offset = h->slot_offset;
     a.k0 = (uint32_t)h->seed; a.k1 = (uint32_t)(h->seed >> 32);
@@ -795,9 +663,8 @@ static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs
     a.cx = h->deferred ? h->cx_alt : h->cx; a.guide = h->deferred ? h->guide_alt : h->guide;
     a.tile_m = h->tile_m; a.tile_W = h->tile_W; a.tile_W2 = h->tile_W2;
     a.tile_m_new = h->tile_m; a.tile_W_new = h->tile_W; a.tile_W2_new = h->tile_W2;
-    if (h->deferred && h->local_table && h->tiles_alt) {   // (what k1_tail_alt says: update_k1_tail)
-        a.tile_m_new = reinterpret_cast<double*>(h->tiles_alt.get()); a.tile_W_new = h->tiles_alt + h->nt; a.tile_W2_new = h->tiles_alt + 2 * (size_t)h->nt;
-    }
+    if (h->deferred && h->local_table && h->tiles_alt)   // (what k1_tail_alt says: update_k1_tail)
+        std::tie(a.tile_m_new, a.tile_W_new, a.tile_W2_new) = tile_views(h->tiles_alt, h->nt);
     // Long row walks (collapsed weights: mp_resolve_draws' BISECT) — which instantiation looks the draws up.  One-double models: always
     // the long-walk one (with MP_WALK_LINEAR = 12 it measures the same as the plain walk on healthy weights — 37.3 us either way,
     // six alternations on one box — and an ESS that drops from 5 x 10^5 to 9 within one step no longer costs a 490 us step; a rule on
@@ -805,7 +672,7 @@ static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs
     // (consecutive slots share a tile's long walks: the 40 % tail of DESIGN.md section 5; under multinomial draws the bisecting instantiation
     // is 4 % slower on C5 and buys nothing).  Both find the same parents: the choice changes time only.
     {
-        const bool wide = !(h->ops->max_normals <= 4 && h->ops->dim_state <= 4);
+        const bool wide = !h->ops->light;
         a.walk_bisect = h->deferred && (wide ? h->draws_lattice : true);
         if (h->walk_bisect_force >= 0) a.walk_bisect = h->walk_bisect_force != 0;   // MP_WALK_BISECT=0 / 1 (tests, A/B): never / always
     }
@@ -870,7 +737,7 @@ static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs
         h->k1_tail.swap(h->k1_tail_alt);
         if (h->local_table) {
             h->tiles_own.swap(h->tiles_alt);
-            h->tile_m = reinterpret_cast<double*>(h->tiles_own.get()); h->tile_W = h->tiles_own + h->nt; h->tile_W2 = h->tiles_own + 2 * (size_t)h->nt;
+            std::tie(h->tile_m, h->tile_W, h->tile_W2) = tile_views(h->tiles_own, h->nt);
         }
         h->draw_pending = false;
         h->pending_shard = false;
@@ -887,17 +754,12 @@ static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs
     h->sh_lazy = false;    // k_propagate wrote x[cur] and logw in slot order ...
     h->rows_fresh = true;  // ... and level 0 of their normalisation
     h->table_fresh = a.aux.tab.ticket != nullptr;   // (built by that launch's last workgroup, or not at all)
-    int32_t rc_ = check_launch("k_propagate");
-    if (rc_ != MP_OK) return rc_;
+    MPCK(check_launch("k_propagate"));
     if (h->flags & MP_PF_RECORD_HISTORY) {
         void* buf = nullptr;
         const size_t bytes = sizeof(double) * h->n * (size_t)h->ops->dim_state;
-        int32_t rch = hist_alloc(h, bytes, &buf);
-        if (rch != MP_OK) return rch;
-        {
-            int32_t rcx = ensure_x(h);
-            if (rcx != MP_OK) return rcx;
-        }
+        MPCK(hist_alloc(h, bytes, &buf));
+        MPCK(ensure_x(h));
         HIPCK(hipMemcpyAsync(buf, h->x[h->cur], bytes, hipMemcpyDeviceToDevice, h->stream));
         h->hist.push_back({0, buf});
     }
@@ -906,11 +768,9 @@ static int32_t launch_propagate(mp_pf* h, const double* args0, const double* obs
 
 // level 0 for the current log-weights when no propagate produced it (after a resample: the weights are zero)
 static int32_t ensure_rows(mp_pf* h) {
-    int32_t rc = materialize(h);
-    if (rc != MP_OK) return rc;
+    MPCK(materialize(h));
     if (h->rows_fresh) return MP_OK;
-    rc = ensure_x(h);
-    if (rc != MP_OK) return rc;
+    MPCK(ensure_x(h));
     {
         LaunchTimer lt(h, MP_K_NORMALIZE_SCAN);
         hipLaunchKernelGGL(k_normalize_tiles, dim3(h->nt), dim3(TILE_THREADS), 0, h->stream, h->logw, h->x[h->cur], h->ops->dim_state, h->n, h->cx, h->guide,
@@ -956,8 +816,7 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
     if (n_particles > 0xFFFFFFFFull) return mp_fail(MP_ERR_INVALID_ARG, "n_particles must fit u32 parent indices");
     struct Cleanup { void operator()(mp_pf* p) const { (void)mp_pf_destroy(p); } };   // an early return frees what was allocated so far
     std::unique_ptr<mp_pf, Cleanup> h(new mp_pf());
-    int32_t rc = make_model(model, h->ops);
-    if (rc != MP_OK) return rc;
+    MPCK(make_model(model, h->ops));
     h->n = n_particles;
     h->n_global = shard ? shard->n_global : n_particles;
     h->slot_offset = shard ? shard->slot_offset : 0;
@@ -1017,9 +876,7 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
     HIPCK(mp_hipMalloc(h->guide, (size_t)h->nt * GUIDE_N));
     HIPCK(mp_hipMalloc(h->parent, n));
     HIPCK(mp_hipMalloc(h->tiles_own, 3 * h->nt));   // packed [3][nt]: m (f64 bits), W, W2 — the unit the shards all-gather
-    h->tile_m = reinterpret_cast<double*>(h->tiles_own.get());
-    h->tile_W = h->tiles_own + h->nt;
-    h->tile_W2 = h->tiles_own + 2 * (size_t)h->nt;
+    std::tie(h->tile_m, h->tile_W, h->tile_W2) = tile_views(h->tiles_own, h->nt);
     HIPCK(mp_hipMalloc(h->scal, 1));
     if (!h->sharded) {
         HIPCK(mp_hipMalloc(h->tab_ticket, 64 / sizeof(unsigned int)));   // a line of its own
@@ -1040,14 +897,10 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
         const int nt_job = (int)((h->n_global + TILE - 1) / TILE);
         const size_t need = table_lds(nt_job, K3_THREADS) + 8192;   // + the per-key counters of the sharded route
         if (need > 48 * 1024) {
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_resample_gather<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_resample_gather<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_resample_gather<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_draw_slots<0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_draw_slots<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_draw_slots<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_finalize_tiles), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shard_targets), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+            const void* const kernels[] = {(const void*)&k_resample_gather<0>, (const void*)&k_resample_gather<1>, (const void*)&k_resample_gather<2>,
+                                           (const void*)&k_draw_slots<0, 0>,   (const void*)&k_draw_slots<0, 1>,   (const void*)&k_draw_slots<0, 2>,
+                                           (const void*)&k_finalize_tiles,     (const void*)&k_shard_targets};
+            for (const void* k : kernels) HIPCK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
         }
     }
     // ParticleSystem::new: log_weights = 0, parents = 0, log_ml_estimate = 0 (particle_filter.rs:44-57)
@@ -1074,10 +927,7 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
     *h->h_scal = init;
     HIPCK(hipMemcpyAsync(h->scal, h->h_scal, sizeof(mp_dev_scalars), hipMemcpyHostToDevice, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    {
-        int32_t rct = update_k1_tail(h.get());
-        if (rct != MP_OK) return rct;
-    }
+    MPCK(update_k1_tail(h.get()));
     *out = h.release();
     return MP_OK;
 }
@@ -1087,10 +937,7 @@ int32_t mp_pf_init_step(mp_pf* h, const double* args0, const double* obs, int32_
     if (n_steps < 1) return mp_fail(MP_ERR_CONSTRAINTS, "init_step needs the constraints of at least one time step");
     if (h->initialised) return mp_fail(MP_ERR_STATE, "init_step called twice");
     HIPCK(hipSetDevice(h->device));
-    for (int k = 0; k < n_steps; ++k) {
-        int32_t rc = launch_propagate(h, args0, obs + (size_t)k * h->ops->dim_obs, k == 0);
-        if (rc != MP_OK) return rc;
-    }
+    for (int k = 0; k < n_steps; ++k) MPCK(launch_propagate(h, args0, obs + (size_t)k * h->ops->dim_obs, k == 0));
     h->initialised = true;
     return MP_OK;
 }
@@ -1100,10 +947,7 @@ int32_t mp_pf_step(mp_pf* h, const double* obs, int32_t n_steps) {
     if (n_steps < 1) return mp_fail(MP_ERR_CONSTRAINTS, "step needs the constraints of at least one time step");
     if (!h->initialised) return mp_fail(MP_ERR_STATE, "step before init_step");
     HIPCK(hipSetDevice(h->device));
-    for (int k = 0; k < n_steps; ++k) {
-        int32_t rc = launch_propagate(h, nullptr, obs + (size_t)k * h->ops->dim_obs, false);
-        if (rc != MP_OK) return rc;
-    }
+    for (int k = 0; k < n_steps; ++k) MPCK(launch_propagate(h, nullptr, obs + (size_t)k * h->ops->dim_obs, false));
     return MP_OK;
 }
 
@@ -1121,6 +965,18 @@ static bool ensure_table(mp_pf* h) {
     return true;
 }
 
+// k_draw_slots<TABMODE, SCHEME> / k_resample_gather<SCHEME> for run-time values of their template arguments
+static decltype(&k_draw_slots<0, 0>) draw_slots_kernel(int tabmode, int scheme) {
+    const int tm = (tabmode == 1 || tabmode == 2) ? tabmode : 0;   // (any other value: the form that builds its table itself)
+    const int sc = scheme == MP_RESAMPLE_MULTINOMIAL ? 0 : scheme == MP_RESAMPLE_SYSTEMATIC ? 1 : 2;
+    static constexpr decltype(&k_draw_slots<0, 0>) kern[3][3] = {{k_draw_slots<0, 0>, k_draw_slots<0, 1>, k_draw_slots<0, 2>},
+                                                                 {k_draw_slots<1, 0>, k_draw_slots<1, 1>, k_draw_slots<1, 2>},
+                                                                 {k_draw_slots<2, 0>, k_draw_slots<2, 1>, k_draw_slots<2, 2>}};
+    return kern[tm][sc];
+}
+static decltype(&k_resample_gather<0>) resample_gather_kernel(int scheme) {
+    return scheme == MP_RESAMPLE_STRATIFIED ? k_resample_gather<2> : scheme == MP_RESAMPLE_SYSTEMATIC ? k_resample_gather<1> : k_resample_gather<0>;
+}
 // k_draw_slots for resample number `rc` of scheme `scheme`: {target, start row} per output slot
 static int32_t launch_draws(mp_pf* h, int32_t scheme, uint32_t rc) {
     {
@@ -1137,21 +993,9 @@ static int32_t launch_draws(mp_pf* h, int32_t scheme, uint32_t rc) {
         static const int draw_wgs = [] { const char* e = mp_diag_env("MP_DRAW_WGS"); return e ? atoi(e) : 512; }();
         // (measured: 2^22 particles / 2048 tiles 55 -> 45 us; at 1024 tiles one workgroup per chunk is the faster form, 26 against 29 us)
         const int draw_grid = (tabmode == 2 || h->nt <= 1024) ? h->nchunks : std::min(h->nchunks, std::max(1, draw_wgs));
-#define MP_LAUNCH_DRAW(TM, SC)                                                                                                              \
-        hipLaunchKernelGGL((k_draw_slots<TM, SC>), dim3(draw_grid), dim3(DRAW_THREADS), lds, h->stream, h->n, h->n_global, h->slot_offset,       \
-                           (uint32_t)h->seed, (uint32_t)(h->seed >> 32), rc, h->S, h->tile_m, h->tile_W, h->tile_W2, h->nt,    \
-                           h->guide, h->dfr_lt, h->dfr_row, h->scal, incl, ratio, head, h->nchunks)
-#define MP_LAUNCH_DRAW_SCHEME(TM)                                                                                                           \
-        do {                                                                                                                                \
-            if (scheme == MP_RESAMPLE_MULTINOMIAL) MP_LAUNCH_DRAW(TM, 0);                                                                   \
-            else if (scheme == MP_RESAMPLE_SYSTEMATIC) MP_LAUNCH_DRAW(TM, 1);                                                               \
-            else MP_LAUNCH_DRAW(TM, 2);                                                                                                     \
-        } while (0)
-        if (tabmode == 1) MP_LAUNCH_DRAW_SCHEME(1);
-        else if (tabmode == 2) MP_LAUNCH_DRAW_SCHEME(2);
-        else MP_LAUNCH_DRAW_SCHEME(0);
-#undef MP_LAUNCH_DRAW_SCHEME
-#undef MP_LAUNCH_DRAW
+        hipLaunchKernelGGL(draw_slots_kernel(tabmode, scheme), dim3(draw_grid), dim3(DRAW_THREADS), lds, h->stream, h->n, h->n_global, h->slot_offset,
+                           (uint32_t)h->seed, (uint32_t)(h->seed >> 32), rc, h->S, h->tile_m, h->tile_W, h->tile_W2, h->nt,
+                           h->guide, h->dfr_lt, h->dfr_row, h->scal, incl, ratio, head, h->nchunks);
     }
     return check_launch("k_draw_slots");
 }
@@ -1176,14 +1020,12 @@ int32_t mp_pf_resample(mp_pf* h, int32_t scheme, double* log_total_weight) {
     if (!h) return mp_fail(MP_ERR_INVALID_ARG, "null handle");
     if (!h->initialised) return mp_fail(MP_ERR_STATE, "resample before init_step");
     if (scheme == MP_RESAMPLE_MULTINOMIAL_SPLIT) scheme = MP_RESAMPLE_MULTINOMIAL;   // (one rank: the same draws, include/modppl_hip.h)
-    if (scheme != MP_RESAMPLE_MULTINOMIAL && scheme != MP_RESAMPLE_SYSTEMATIC && scheme != MP_RESAMPLE_STRATIFIED)
-        return mp_fail(MP_ERR_INVALID_ARG, "unknown resampling scheme");
+    MPCK(check_scheme(scheme));
     if (h->sharded) return mp_fail(MP_ERR_STATE, "sharded handle: resample runs through the mp_pf_shard_* phases");
     HIPCK(hipSetDevice(h->device));
     h->lazy_pending = false;   // log_weights.fill(0.) and new parents (particle_filter.rs:109-114): what the last step did not store is dead
     h->sync_loop = log_total_weight != nullptr;
-    int32_t rc = ensure_rows(h);
-    if (rc != MP_OK) return rc;
+    MPCK(ensure_rows(h));
     h->parents_deferred = false;   // this resample's parents replace whatever was still waiting to be read
     h->sh_parents_lazy = false;
     h->sh_recv = false;
@@ -1197,8 +1039,7 @@ int32_t mp_pf_resample(mp_pf* h, int32_t scheme, double* log_total_weight) {
             HIPCK(mp_hipMalloc(h->cx_alt, (size_t)h->nt * TILE));
             HIPCK(mp_hipMalloc(h->guide_alt, (size_t)h->nt * GUIDE_N));
             if (h->local_table) HIPCK(mp_hipMalloc(h->tiles_alt, 3 * h->nt));
-            int32_t rct = update_k1_tail(h);
-            if (rct != MP_OK) return rct;
+            MPCK(update_k1_tail(h));
         }
         const mp_tab tab = tab_of(h);
         // ... and for kernels whose lanes own one Philox block's two slots, not even the draws are made here: an asynchronous
@@ -1213,31 +1054,17 @@ int32_t mp_pf_resample(mp_pf* h, int32_t scheme, double* log_total_weight) {
             h->pending_scheme = scheme;
             peek_L = log_total_weight != nullptr;
         } else {
-            rc = launch_draws(h, scheme, h->resample_count);
-            if (rc != MP_OK) return rc;
+            MPCK(launch_draws(h, scheme, h->resample_count));
         }
         drawn_only = true;
     } else {
         LaunchTimer lt(h, MP_K_RESAMPLE_GATHER);
-        if (scheme == MP_RESAMPLE_STRATIFIED) {
-            hipLaunchKernelGGL(k_resample_gather<2>, dim3(h->k3_grid), dim3(KG_THREADS), table_lds(h->nt, KG_THREADS), h->stream, h->n, h->n,
-                               h->n_global, h->slot_offset, (uint32_t)MP_DOM_RESAMPLE, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), h->resample_count,
-                               h->S, d, h->cx, h->guide, h->tile_m, h->tile_W, h->tile_W2, h->nt, h->x[h->cur], h->x[h->cur ^ 1], h->parent, h->logw,
-                               h->scal);
-        } else if (scheme == MP_RESAMPLE_SYSTEMATIC) {
-            hipLaunchKernelGGL(k_resample_gather<1>, dim3(h->k3_grid), dim3(KG_THREADS), table_lds(h->nt, KG_THREADS), h->stream, h->n, h->n,
-                               h->n_global, h->slot_offset, (uint32_t)MP_DOM_RESAMPLE, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), h->resample_count,
-                               h->S, d, h->cx, h->guide, h->tile_m, h->tile_W, h->tile_W2, h->nt, h->x[h->cur], h->x[h->cur ^ 1], h->parent, h->logw,
-                               h->scal);
-        } else {
-            hipLaunchKernelGGL(k_resample_gather<0>, dim3(h->k3_grid), dim3(KG_THREADS), table_lds(h->nt, KG_THREADS), h->stream, h->n, h->n,
-                               h->n_global, h->slot_offset, (uint32_t)MP_DOM_RESAMPLE, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), h->resample_count,
-                               h->S, d, h->cx, h->guide, h->tile_m, h->tile_W, h->tile_W2, h->nt, h->x[h->cur], h->x[h->cur ^ 1], h->parent, h->logw,
-                               h->scal);
-        }
+        hipLaunchKernelGGL(resample_gather_kernel(scheme), dim3(h->k3_grid), dim3(KG_THREADS), table_lds(h->nt, KG_THREADS), h->stream, h->n, h->n,
+                           h->n_global, h->slot_offset, (uint32_t)MP_DOM_RESAMPLE, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), h->resample_count,
+                           h->S, d, h->cx, h->guide, h->tile_m, h->tile_W, h->tile_W2, h->nt, h->x[h->cur], h->x[h->cur ^ 1], h->parent, h->logw,
+                           h->scal);
     }
-    rc = check_launch("resample kernels");
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("resample kernels"));
     h->draws_lattice = scheme != MP_RESAMPLE_MULTINOMIAL;
     if (drawn_only) h->deferred = true;   // x[cur] is the (stale) pre-resample state until the draws are looked up
     else {
@@ -1247,11 +1074,9 @@ int32_t mp_pf_resample(mp_pf* h, int32_t scheme, double* log_total_weight) {
     h->rows_fresh = false;            // the log-weights are now all zero
     h->resample_count += 1;
     if (h->flags & MP_PF_RECORD_HISTORY) {
-        rc = materialize(h);
-        if (rc != MP_OK) return rc;
+        MPCK(materialize(h));
         void* buf = nullptr;
-        rc = hist_alloc(h, sizeof(uint32_t) * h->n, &buf);
-        if (rc != MP_OK) return rc;
+        MPCK(hist_alloc(h, sizeof(uint32_t) * h->n, &buf));
         HIPCK(hipMemcpyAsync(buf, h->parent, sizeof(uint32_t) * h->n, hipMemcpyDeviceToDevice, h->stream));
         h->hist.push_back({1, buf});
     }
@@ -1263,18 +1088,14 @@ int32_t mp_pf_resample(mp_pf* h, int32_t scheme, double* log_total_weight) {
             h->peek_seq += 1;
             hipLaunchKernelGGL(k_peek_level1, dim3(1), dim3(1024), 0, h->stream, (const double*)h->tile_m, (const u64*)h->tile_W, (const u64*)h->tile_W2, h->nt, h->S,
                                h->scal, h->d_mirror, h->peek_seq);
-            rc = check_launch("k_peek_level1");
-            if (rc != MP_OK) return rc;
+            MPCK(check_launch("k_peek_level1"));
         }
         h->peek_valid = false;
-        rc = wait_seq(h, &h->h_mirror->peek_seq, h->peek_seq, "resample");
-        if (rc != MP_OK) return rc;
-        if (h->h_mirror->peek_degenerate)
-            return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+        MPCK(wait_seq(h, &h->h_mirror->peek_seq, h->peek_seq, "resample"));
+        if (h->h_mirror->peek_degenerate) return mp_fail_degenerate();
         *log_total_weight = h->h_mirror->peek_L;
     } else if (log_total_weight) {
-        rc = fetch_scalars(h);
-        if (rc != MP_OK) return rc;
+        MPCK(fetch_scalars(h));
         *log_total_weight = h->h_scal->L;
     }
     return MP_OK;
@@ -1282,12 +1103,10 @@ int32_t mp_pf_resample(mp_pf* h, int32_t scheme, double* log_total_weight) {
 
 static int32_t query(mp_pf* h) {
     if (h->sharded) return mp_fail(MP_ERR_STATE, "sharded handle: use mp_pf_shard_query");
-    int32_t rc = ensure_rows(h);
-    if (rc != MP_OK) return rc;
+    MPCK(ensure_rows(h));
     hipLaunchKernelGGL(k_finalize_tiles, dim3(1), dim3(K3_THREADS), table_lds(h->nt, K3_THREADS), h->stream, h->tile_m, h->tile_W, h->tile_W2, h->nt,
                        h->S, h->n_global, 1, h->scal);
-    rc = check_launch("k_finalize_tiles");
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("k_finalize_tiles"));
     return fetch_scalars(h);
 }
 
@@ -1299,22 +1118,18 @@ int32_t mp_pf_effective_sample_size(mp_pf* h, int32_t ess_mode, double* out) {
             // the value of the last resample's normalisation (particle_filter.rs:98-100 reads buffers only `resample` refreshes): in
             // host-mapped memory as soon as whoever makes that resample's draws has folded it — the first workgroup of the step
             // that follows an asynchronous resample does so in its first microseconds, so this does not wait for the step to end
-            int32_t rc = flush_draws(h);
-            if (rc != MP_OK) return rc;
-            rc = wait_seq(h, &h->h_mirror->fold_seq, h->resample_count, "effective_sample_size");
-            if (rc != MP_OK) return rc;
+            MPCK(flush_draws(h));
+            MPCK(wait_seq(h, &h->h_mirror->fold_seq, h->resample_count, "effective_sample_size"));
             *out = h->h_mirror->ess_stale;
             return MP_OK;
         }
-        int32_t rc = fetch_scalars(h);
-        if (rc != MP_OK) return rc;
+        MPCK(fetch_scalars(h));
         *out = h->h_scal->ess_stale;
         return MP_OK;
     }
     if (ess_mode != MP_ESS_FRESH) return mp_fail(MP_ERR_INVALID_ARG, "unknown ess mode");
     if (!h->initialised) return mp_fail(MP_ERR_STATE, "effective_sample_size(FRESH) before init_step");
-    int32_t rc = query(h);
-    if (rc != MP_OK) return rc;
+    MPCK(query(h));
     *out = h->h_scal->ess_fresh;
     return MP_OK;
 }
@@ -1326,8 +1141,7 @@ int32_t mp_pf_resample_if_ess_below(mp_pf* h, int32_t scheme, double ess_fractio
     if (!(ess_fraction >= 0.) || ess_fraction > 1.) return mp_fail(MP_ERR_INVALID_ARG, "ess_fraction must be in [0, 1]");
     if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, "sharded filters decide from mp_pf_shard_query_packed on every rank");
     double ess = 0.;
-    int32_t rc = mp_pf_effective_sample_size(h, MP_ESS_FRESH, &ess);
-    if (rc != MP_OK) return rc;
+    MPCK(mp_pf_effective_sample_size(h, MP_ESS_FRESH, &ess));
     if (ess_out) *ess_out = ess;
     *resampled = (ess < ess_fraction * (double)h->n) ? 1 : 0;
     if (!*resampled) return MP_OK;
@@ -1337,8 +1151,7 @@ int32_t mp_pf_resample_if_ess_below(mp_pf* h, int32_t scheme, double ess_fractio
 int32_t mp_pf_log_marginal_likelihood_estimate(mp_pf* h, double* out) {
     if (!h || !out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     HIPCK(hipSetDevice(h->device));
-    int32_t rc = query(h);
-    if (rc != MP_OK) return rc;
+    MPCK(query(h));
     *out = h->h_scal->lml_fresh;
     return MP_OK;
 }
@@ -1346,8 +1159,8 @@ int32_t mp_pf_log_marginal_likelihood_estimate(mp_pf* h, double* out) {
 int32_t mp_pf_read_state(mp_pf* h, double* x_out) {
     if (!h || !x_out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     HIPCK(hipSetDevice(h->device));
-    { int32_t rcm = materialize(h); if (rcm != MP_OK) return rcm; }
-    { int32_t rcx = ensure_x(h); if (rcx != MP_OK) return rcx; }
+    MPCK(materialize(h));
+    MPCK(ensure_x(h));
     const int d = h->ops->dim_state;   // device layout = host layout: particle-major x[i][d]
     HIPCK(hipMemcpyAsync(x_out, h->x[h->cur], sizeof(double) * h->n * d, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
@@ -1357,8 +1170,8 @@ int32_t mp_pf_read_state(mp_pf* h, double* x_out) {
 int32_t mp_pf_read_log_weights(mp_pf* h, double* out) {
     if (!h || !out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     HIPCK(hipSetDevice(h->device));
-    { int32_t rcm = materialize(h); if (rcm != MP_OK) return rcm; }
-    { int32_t rcl = ensure_lazy(h); if (rcl != MP_OK) return rcl; }
+    MPCK(materialize(h));
+    MPCK(ensure_lazy(h));
     HIPCK(hipMemcpyAsync(out, h->logw, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
     return MP_OK;
@@ -1367,23 +1180,21 @@ int32_t mp_pf_read_log_weights(mp_pf* h, double* out) {
 int32_t mp_pf_read_parents(mp_pf* h, uint32_t* out) {
     if (!h || !out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     HIPCK(hipSetDevice(h->device));
-    { int32_t rcm = materialize(h); if (rcm != MP_OK) return rcm; }
-    { int32_t rcl = ensure_lazy(h); if (rcl != MP_OK) return rcl; }
+    MPCK(materialize(h));
+    MPCK(ensure_lazy(h));
     // a step after a lazy resample moved the states on but left the parents where the resample put them
     if (h->parents_deferred) {
         hipLaunchKernelGGL(k_resolve_slots<false>, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->n, h->ops->dim_state,
                            (const u64*)h->dfr_lt, (const uint32_t*)h->dfr_row, (const mp_cx*)h->cx_alt, (const double*)nullptr, (double*)nullptr, h->parent,
                            (double*)nullptr, h->sh_recv ? h->sh_rows : (const double*)nullptr, h->slot_offset);
         h->parents_deferred = false;
-        int32_t rcp = check_launch("k_resolve_slots");
-        if (rcp != MP_OK) return rcp;
+        MPCK(check_launch("k_resolve_slots"));
     }
     if (h->sh_parents_lazy) {
         hipLaunchKernelGGL(k_shard_adopt_parents, dim3((unsigned)((h->n + SH_THREADS - 1) / SH_THREADS)), dim3(SH_THREADS), 0, h->stream, h->n,
                            h->ops->dim_state, h->sh_rows, h->sh_req_slot, h->slot_offset, h->parent);
         h->sh_parents_lazy = false;
-        int32_t rcp = check_launch("k_shard_adopt_parents");
-        if (rcp != MP_OK) return rcp;
+        MPCK(check_launch("k_shard_adopt_parents"));
     }
     HIPCK(hipMemcpyAsync(out, h->parent, sizeof(uint32_t) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
@@ -1402,9 +1213,9 @@ int32_t mp_pf_moments(mp_pf* h, double* mean_out, double* cov_out) {
     const int d = h->ops->dim_state;
     if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_moments: no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
     HIPCK(hipSetDevice(h->device));
-    { int32_t rcm = materialize(h); if (rcm != MP_OK) return rcm; }
-    { int32_t rcx = ensure_x(h); if (rcx != MP_OK) return rcx; }
-    { int32_t rcl = ensure_lazy(h); if (rcl != MP_OK) return rcl; }
+    MPCK(materialize(h));
+    MPCK(ensure_x(h));
+    MPCK(ensure_lazy(h));
     const int R = d <= 4 ? 8 : 4;   // mom_run<D>::R
     const int npairs = d * (d + 1) / 2;
     const u64 nb = (h->n + (u64)MOM_THREADS * R - 1) / ((u64)MOM_THREADS * R);          // workgroups of the two moment passes
@@ -1431,12 +1242,11 @@ int32_t mp_pf_moments(mp_pf* h, double* mean_out, double* cov_out) {
         }
         mom_close<mom_add>(h->stream, buf, nb, pass == 1 ? (unsigned)(d + 1) : (unsigned)npairs, pass == 1 ? res + 1 : res + 2 + 2 * d);
     }
-    { int32_t rck = check_launch("mp_pf_moments kernels"); if (rck != MP_OK) return rck; }
+    MPCK(check_launch("mp_pf_moments kernels"));
     HIPCK(hipMemcpyAsync(h->mom_host, res, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
     HIPCK(stream_wait(h->stream));
     const double* r = h->mom_host;
-    if (r[0] == -MP_INF)
-        return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+    if (r[0] == -MP_INF) return mp_fail_degenerate();
     const double A = r[1];
     // without a covariance pass nobody has formed the means on the device: the same IEEE division here
     for (int j = 0; j < d; ++j) mean_out[j] = cov_out ? r[2 + d + j] : r[2 + j] / A;
@@ -1454,8 +1264,7 @@ int32_t mp_pf_shard_tiles(mp_pf* h, double* d_tile_m, uint64_t* d_tile_W, uint64
     if (!h || !d_tile_m || !d_tile_W || !d_tile_W2) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     if (!h->initialised) return mp_fail(MP_ERR_STATE, "resample before init_step");
     HIPCK(hipSetDevice(h->device));
-    int32_t rc = ensure_rows(h);
-    if (rc != MP_OK) return rc;
+    MPCK(ensure_rows(h));
     HIPCK(hipMemcpyAsync(d_tile_m, h->tile_m, sizeof(double) * h->nt, hipMemcpyDeviceToDevice, h->stream));
     HIPCK(hipMemcpyAsync(d_tile_W, h->tile_W, sizeof(u64) * h->nt, hipMemcpyDeviceToDevice, h->stream));
     HIPCK(hipMemcpyAsync(d_tile_W2, h->tile_W2, sizeof(u64) * h->nt, hipMemcpyDeviceToDevice, h->stream));
@@ -1465,17 +1274,12 @@ int32_t mp_pf_shard_tiles(mp_pf* h, double* d_tile_m, uint64_t* d_tile_W, uint64
 int32_t mp_pf_shard_route(mp_pf* h, int32_t scheme, const double* d_tm_all, const uint64_t* d_tW_all, const uint64_t* d_tW2_all, int32_t world,
                           int32_t rank, uint64_t* d_req_out, int64_t* send_counts) {
     if (!h || !d_tm_all || !d_tW_all || !d_tW2_all || !d_req_out || !send_counts) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
-    if (scheme != MP_RESAMPLE_MULTINOMIAL && scheme != MP_RESAMPLE_SYSTEMATIC && scheme != MP_RESAMPLE_STRATIFIED)
-        return mp_fail(MP_ERR_INVALID_ARG, "unknown resampling scheme");
-    if (world < 1 || world > SH_MAX_WORLD || rank < 0 || rank >= world) return mp_fail(MP_ERR_INVALID_ARG, "1 <= world <= 64, 0 <= rank < world");
-    if ((u64)world * h->n != h->n_global) return mp_fail(MP_ERR_INVALID_ARG, "equal tile-aligned shards: world * n_particles must equal n_global");
+    MPCK(check_scheme(scheme));
+    MPCK(check_world(h, world, rank));
     HIPCK(hipSetDevice(h->device));
     const int nblk = (int)((h->n + SH_THREADS - 1) / SH_THREADS);
     const int nt_all = h->nt * world;
-    {
-        int32_t rcs = shard_scratch(h, world, h->sh_cap ? h->sh_cap : 1);
-        if (rcs != MP_OK) return rcs;
-    }
+    MPCK(shard_scratch(h, world, h->sh_cap ? h->sh_cap : 1));
     {
         LaunchTimer lt(h, MP_K_RESAMPLE_GATHER);
         const size_t lds = table_lds(nt_all, SH_THREADS) + sizeof(uint32_t) * SH_MAX_WORLD;
@@ -1486,13 +1290,11 @@ int32_t mp_pf_shard_route(mp_pf* h, int32_t scheme, const double* d_tm_all, cons
         hipLaunchKernelGGL(k_shard_pack, dim3(nblk), dim3(SH_THREADS), 0, h->stream, h->n, h->sh_dest, h->sh_lt, h->sh_tile, h->sh_blockoff, h->sh_counts,
                            world, (u64*)d_req_out, h->sh_req_slot);
     }
-    int32_t rc = check_launch("k_shard_targets/offsets/pack");
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("k_shard_targets/offsets/pack"));
     // the finalisation of this normalisation (L, ESS, log-ML) only needs the gathered tiles
     hipLaunchKernelGGL(k_finalize_tiles, dim3(1), dim3(K3_THREADS), table_lds(nt_all, K3_THREADS), h->stream, d_tm_all, (const u64*)d_tW_all,
                        (const u64*)d_tW2_all, nt_all, h->S, h->n_global, 0, h->scal);
-    rc = check_launch("k_finalize_tiles");
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("k_finalize_tiles"));
     HIPCK(hipMemcpyAsync(h->h_counts, h->sh_counts, sizeof(long long) * world, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
     for (int r = 0; r < world; ++r) send_counts[r] = h->h_counts[r];
@@ -1504,7 +1306,7 @@ int32_t mp_pf_shard_resolve(mp_pf* h, const uint64_t* d_req_in, uint64_t n_req, 
     HIPCK(hipSetDevice(h->device));
     // (before the early return: mp_pf_shard_scatter flips `cur` whether or not this rank was asked for rows, and a dim_state-1
     // handle's current states may live in the row table only)
-    { int32_t rcx = ensure_x(h); if (rcx != MP_OK) return rcx; }
+    MPCK(ensure_x(h));
     if (n_req == 0) return MP_OK;
     if (!d_req_in || !d_rows_out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     int grid = (int)std::min<u64>((n_req + K3_THREADS - 1) / K3_THREADS, (u64)K3_MAX_BLOCKS);
@@ -1525,8 +1327,7 @@ int32_t mp_pf_shard_scatter(mp_pf* h, const double* d_rows_in, double* log_total
         hipLaunchKernelGGL(k_shard_scatter, dim3((unsigned)((h->n + SH_THREADS - 1) / SH_THREADS)), dim3(SH_THREADS), 0, h->stream, h->n,
                            h->ops->dim_state, d_rows_in, h->sh_req_slot, h->x[h->cur ^ 1], h->parent, h->logw);
     }
-    int32_t rc = check_launch("k_shard_scatter");
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("k_shard_scatter"));
     h->parents_deferred = false;   // k_shard_scatter wrote parent[]
     h->sh_parents_lazy = false;
     h->cur ^= 1;
@@ -1534,8 +1335,7 @@ int32_t mp_pf_shard_scatter(mp_pf* h, const double* d_rows_in, double* log_total
     h->rows_fresh = false;
     h->resample_count += 1;
     if (log_total_weight) {
-        rc = fetch_scalars(h);
-        if (rc != MP_OK) return rc;
+        MPCK(fetch_scalars(h));
         *log_total_weight = h->h_scal->L;
     }
     return MP_OK;
@@ -1548,10 +1348,8 @@ int32_t mp_pf_shard_query(mp_pf* h, const double* d_tm_all, const uint64_t* d_tW
     const int nt_all = h->nt * world;
     hipLaunchKernelGGL(k_finalize_tiles, dim3(1), dim3(K3_THREADS), table_lds(nt_all, K3_THREADS), h->stream, d_tm_all, (const u64*)d_tW_all,
                        (const u64*)d_tW2_all, nt_all, h->S, h->n_global, 1, h->scal);
-    int32_t rc = check_launch("k_finalize_tiles");
-    if (rc != MP_OK) return rc;
-    rc = fetch_scalars(h);
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("k_finalize_tiles"));
+    MPCK(fetch_scalars(h));
     if (log_ml) *log_ml = h->h_scal->lml_fresh;
     if (ess) *ess = h->h_scal->ess_fresh;
     return MP_OK;
@@ -1603,9 +1401,7 @@ int32_t mp_pf_shard_bind_tiles(mp_pf* h, uint64_t* d_tiles) {
     HIPCK(hipSetDevice(h->device));
     HIPCK(hipMemcpyAsync(d_tiles, h->tile_m, sizeof(u64) * 3 * h->nt, hipMemcpyDeviceToDevice, h->stream));
     h->local_table = false;   // (a handle driven through the shard phases: its tile scalars live in the caller's buffer, not in a pair of the library's)
-    h->tile_m = reinterpret_cast<double*>(d_tiles);
-    h->tile_W = (u64*)d_tiles + h->nt;
-    h->tile_W2 = (u64*)d_tiles + 2 * (size_t)h->nt;
+    std::tie(h->tile_m, h->tile_W, h->tile_W2) = tile_views((u64*)d_tiles, h->nt);
     return update_k1_tail(h);
 }
 
@@ -1613,8 +1409,7 @@ int32_t mp_pf_shard_tiles_packed(mp_pf* h, uint64_t* d_tiles_out) {
     if (!h || !d_tiles_out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     if (!h->initialised) return mp_fail(MP_ERR_STATE, "resample before init_step");
     HIPCK(hipSetDevice(h->device));
-    int32_t rc = ensure_rows(h);
-    if (rc != MP_OK) return rc;
+    MPCK(ensure_rows(h));
     if ((void*)d_tiles_out != (void*)h->tile_m)   // a bound buffer already holds them
         HIPCK(hipMemcpyAsync(d_tiles_out, h->tile_m, sizeof(u64) * 3 * h->nt, hipMemcpyDeviceToDevice, h->stream));
     return MP_OK;
@@ -1652,15 +1447,12 @@ static void launch_shard_table(mp_pf* h, const u64* d_tiles_all, int world, unsi
 int32_t mp_pf_shard_route_fixed(mp_pf* h, int32_t scheme, const uint64_t* d_tiles_all, int32_t world, int32_t rank, uint64_t capacity,
                                 uint64_t* d_req_out) {
     if (!h || !d_tiles_all || !d_req_out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
-    if (scheme != MP_RESAMPLE_MULTINOMIAL && scheme != MP_RESAMPLE_SYSTEMATIC && scheme != MP_RESAMPLE_STRATIFIED)
-        return mp_fail(MP_ERR_INVALID_ARG, "unknown resampling scheme");
-    if (world < 1 || world > SH_MAX_WORLD || rank < 0 || rank >= world) return mp_fail(MP_ERR_INVALID_ARG, "1 <= world <= 64, 0 <= rank < world");
-    if ((u64)world * h->n != h->n_global) return mp_fail(MP_ERR_INVALID_ARG, "equal tile-aligned shards: world * n_particles must equal n_global");
+    MPCK(check_scheme(scheme));
+    MPCK(check_world(h, world, rank));
     if (capacity == 0) return mp_fail(MP_ERR_INVALID_ARG, "capacity must be > 0");
     if ((u64)world * SH_BINS * capacity >= (1ull << 31)) return mp_fail(MP_ERR_INVALID_ARG, "exchange buffer rows must be < 2^31 (row indices carry a flag bit)");
     HIPCK(hipSetDevice(h->device));
-    int32_t rc = shard_scratch(h, world, capacity);
-    if (rc != MP_OK) return rc;
+    MPCK(shard_scratch(h, world, capacity));
     const int nt_all = h->nt * world;
     {
         LaunchTimer lt(h, MP_K_BIN_DRAWS);
@@ -1679,7 +1471,7 @@ int32_t mp_pf_shard_resolve_fixed(mp_pf* h, const uint64_t* d_req_in, int32_t wo
     if (world < 1 || world > SH_MAX_WORLD || capacity == 0) return mp_fail(MP_ERR_INVALID_ARG, "1 <= world <= 64, capacity > 0");
     if (!h->h_pub) return mp_fail(MP_ERR_STATE, "shard_resolve_fixed before shard_route_fixed");
     HIPCK(hipSetDevice(h->device));
-    { int32_t rcx = ensure_x(h); if (rcx != MP_OK) return rcx; }
+    MPCK(ensure_x(h));
     // workgroups per (asking rank, eighth): enough to fill the chip, each takes K3_THREADS * K3_ITEMS requests per round
     const u64 per = (u64)K3_THREADS * SHR_ITEMS;
     const unsigned groups = (unsigned)std::max<u64>(1, std::min<u64>((capacity + per - 1) / per, std::max<u64>(1, 512 / (u64)world)));
@@ -1689,8 +1481,7 @@ int32_t mp_pf_shard_resolve_fixed(mp_pf* h, const uint64_t* d_req_in, int32_t wo
                            h->ops->dim_state, (const u64*)d_req_in, h->cx, h->guide, h->tile_W, h->x[h->cur], d_rows_out, h->sh_overflow);
         hipLaunchKernelGGL(k_shard_publish, dim3(1), dim3(1), 0, h->stream, h->sh_overflow, h->scal, h->d_pub);
     }
-    int32_t rc = check_launch("k_shard_resolve_binned");
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("k_shard_resolve_binned"));
     HIPCK(hipEventRecord(h->ev_resolved, h->stream));   // mp_pf_shard_commit_fixed waits for this, not for what follows on the stream
     return MP_OK;
 }
@@ -1711,8 +1502,7 @@ int32_t mp_pf_shard_commit_fixed(mp_pf* h, const double* d_rows_in, double* log_
     }
     // all weights -inf: no rank owns a draw, the request slots were never written — nothing may be committed (the next
     // propagate would read rows[inv[i]] out of bounds); the reference panics here (categorical.rs:23)
-    if (h->h_pub->degenerate)
-        return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+    if (h->h_pub->degenerate) return mp_fail_degenerate();
     // traces[i] = traces[parents[i]].clone() (particle_filter.rs:109-113), lazily: the next propagate reads slot i's state
     // from row sh_req_slot[i] of the exchange buffer; anything else first copies states and parents into slot order.
     h->sh_rows = d_rows_in;
@@ -1724,8 +1514,7 @@ int32_t mp_pf_shard_commit_fixed(mp_pf* h, const double* d_rows_in, double* log_
     h->rows_fresh = false;
     h->resample_count += 1;
     if (log_total_weight) {
-        if (h->h_pub->degenerate)
-            return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+        if (h->h_pub->degenerate) return mp_fail_degenerate();
         *log_total_weight = h->h_pub->L;
     }
     return MP_OK;
@@ -1762,8 +1551,7 @@ static int32_t owned_scratch(mp_pf* h, int world) {
         HIPCK(mp_hipMalloc(h->cx_alt, (size_t)h->nt * TILE));
         HIPCK(mp_hipMalloc(h->guide_alt, (size_t)h->nt * GUIDE_N));
         if (h->local_table) HIPCK(mp_hipMalloc(h->tiles_alt, 3 * h->nt));
-        int32_t rct = update_k1_tail(h);
-        if (rct != MP_OK) return rct;
+        MPCK(update_k1_tail(h));
     }
     HIPCK(mp_hipMalloc(h->ow_sccnt, (size_t)h->ow_nsc));
     HIPCK(mp_hipMalloc(h->ow_base, (size_t)h->ow_nsc));
@@ -1847,18 +1635,13 @@ static int32_t shard_owned_count_impl(mp_pf* h, int32_t scheme, const uint64_t* 
                                       uint64_t* counts_out, double* fuse_send) {
     if (!h || !d_tiles_all) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     if (!h->initialised) return mp_fail(MP_ERR_STATE, "resample before init_step");
-    if (scheme != MP_RESAMPLE_MULTINOMIAL && scheme != MP_RESAMPLE_SYSTEMATIC && scheme != MP_RESAMPLE_STRATIFIED && scheme != MP_RESAMPLE_MULTINOMIAL_SPLIT)
-        return mp_fail(MP_ERR_INVALID_ARG, "unknown resampling scheme");
-    if (world < 1 || world > SH_MAX_WORLD || rank < 0 || rank >= world) return mp_fail(MP_ERR_INVALID_ARG, "1 <= world <= 64, 0 <= rank < world");
-    if ((u64)world * h->n != h->n_global) return mp_fail(MP_ERR_INVALID_ARG, "equal tile-aligned shards: world * n_particles must equal n_global");
+    MPCK(check_scheme(scheme, true));
+    MPCK(check_world(h, world, rank));
     if (h->n_global >= (1ull << 32)) return mp_fail(MP_ERR_INVALID_ARG, "owner-keeps exchange: n_global must be < 2^32");
     HIPCK(hipSetDevice(h->device));
-    int32_t rc = ensure_rows(h);
-    if (rc != MP_OK) return rc;
-    rc = shard_scratch(h, world, h->sh_cap ? h->sh_cap : 1);
-    if (rc != MP_OK) return rc;
-    rc = owned_scratch(h, world);
-    if (rc != MP_OK) return rc;
+    MPCK(ensure_rows(h));
+    MPCK(shard_scratch(h, world, h->sh_cap ? h->sh_cap : 1));
+    MPCK(owned_scratch(h, world));
     h->ow_rank = rank;
     h->ow_self = false;
     h->ow_placed = false;
@@ -1895,14 +1678,12 @@ static int32_t shard_owned_count_impl(mp_pf* h, int32_t scheme, const uint64_t* 
             h->ow_placed_cap = capacity;
             h->ow_placed_send = fuse_send;
         }
-        rc = check_launch("self-drawn resample: table / plan");
-        if (rc != MP_OK) return rc;
+        MPCK(check_launch("self-drawn resample: table / plan"));
         if (counts_out && world == 1) {
             counts_out[0] = h->n;
         } else if (counts_out) {
             HIPCK(stream_wait(h->stream));
-            if (h->h_pub->degenerate)
-                return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+            if (h->h_pub->degenerate) return mp_fail_degenerate();
             for (int r = 0; r < world; ++r) counts_out[r] = h->h_pub->counts[r];
         }
         return MP_OK;
@@ -1945,16 +1726,13 @@ static int32_t shard_owned_count_impl(mp_pf* h, int32_t scheme, const uint64_t* 
         if (world > 1) hipLaunchKernelGGL(k_shard_own_plan, dim3(1), dim3(SHP_THREADS), 0, h->stream, pa);
     }
     h->ow_scheme = scheme;
-    rc = check_launch("shard_owned_count kernels");
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("shard_owned_count kernels"));
     if (counts_out && world == 1) {
-        rc = fetch_scalars(h);   // degenerate weights are reported here, as by the plan's verdict in larger worlds
-        if (rc != MP_OK) return rc;
+        MPCK(fetch_scalars(h));   // degenerate weights are reported here, as by the plan's verdict in larger worlds
         counts_out[0] = h->n;
     } else if (counts_out) {   // exact sizes: the caller sizes its buffers from the counts (the stream drains: every field of h_pub is out)
         HIPCK(stream_wait(h->stream));
-        if (h->h_pub->degenerate)
-            return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+        if (h->h_pub->degenerate) return mp_fail_degenerate();
         for (int r = 0; r < world; ++r) counts_out[r] = h->h_pub->counts[r];
     }
     return MP_OK;
@@ -1971,8 +1749,7 @@ int32_t mp_pf_shard_owned_count_expand(mp_pf* h, int32_t scheme, const uint64_t*
     if (capacity == 0) return mp_fail(MP_ERR_INVALID_ARG, "count_expand is the equal-split form: capacity must be > 0 (exact sizes: count, then expand)");
     if (world >= 1 && recv_rows != (uint64_t)world * capacity) return mp_fail(MP_ERR_INVALID_ARG, "fixed capacity: recv_rows must be world * capacity");
     if (recv_rows + h->n >= (1ull << 31)) return mp_fail(MP_ERR_INVALID_ARG, "exchange buffer rows must be < 2^31 (row indices carry a flag bit)");
-    int32_t rc = shard_owned_count_impl(h, scheme, d_tiles_all, world, rank, capacity, nullptr, d_send_out);
-    if (rc != MP_OK) return rc;
+    MPCK(shard_owned_count_impl(h, scheme, d_tiles_all, world, rank, capacity, nullptr, d_send_out));
     return mp_pf_shard_owned_expand(h, world, rank, capacity, d_send_out, d_rows, recv_rows);
 }
 
@@ -1992,10 +1769,7 @@ int32_t mp_pf_shard_owned_expand(mp_pf* h, int32_t world, int32_t rank, uint64_t
         // after an overflow verdict comes with another buffer and capacity 0: placed again below)
         if (h->ow_placed && self_k1_draws(h) && capacity == h->ow_placed_cap && d_send_out == h->ow_placed_send) return MP_OK;
         LaunchTimer lt(h, MP_K_RESAMPLE_GATHER);
-        if (!self_k1_draws(h)) {
-            int32_t rcs = launch_self_draws(h, h->ow_scheme, h->resample_count, world, rank);
-            if (rcs != MP_OK) return rcs;
-        }
+        if (!self_k1_draws(h)) MPCK(launch_self_draws(h, h->ow_scheme, h->resample_count, world, rank));
         if (world > 1) {
             auto kern = (h->ow_scheme == MP_RESAMPLE_MULTINOMIAL_SPLIT) ? k_shard_self_place<false> : k_shard_self_place<true>;
             hipLaunchKernelGGL(kern, dim3(64), dim3(256), 0, h->stream, self_place_args(h, rank, capacity, d_send_out), h->n_global, (uint32_t)h->seed,
@@ -2033,8 +1807,7 @@ int32_t mp_pf_shard_owned_commit(mp_pf* h, const double* d_rows, double* log_tot
             h->ow_solo_folded = true;
         }
         if (slow) {   // no plan ran: the scalars themselves
-            int32_t rcs = fetch_scalars(h);
-            if (rcs != MP_OK) return rcs;
+            MPCK(fetch_scalars(h));
             L_one = h->h_scal->L;
             if (counts_out) counts_out[0] = h->n;
         }
@@ -2042,14 +1815,11 @@ int32_t mp_pf_shard_owned_commit(mp_pf* h, const double* d_rows, double* log_tot
         HIPCK(stream_wait(h->stream));
         flags = (unsigned)(h->h_pub->verdict & 0xFFu);
         if ((h->h_pub->verdict >> 8) != h->ow_seq) return mp_fail(MP_ERR_HIP, "owner-keeps plan: the stream drained without a verdict");
-    } else if (h->ow_world > 1) {
-        int32_t rcw = owned_wait_plan(h, &flags);
-        if (rcw != MP_OK) return rcw;
-    }
+    } else if (h->ow_world > 1) MPCK(owned_wait_plan(h, &flags));
     if (counts_out && h->ow_world > 1)
         for (int r = 0; r < h->ow_world; ++r) counts_out[r] = h->h_pub->counts[r];
     if (flags & 2u)   // before anything is committed: with Q == 0 no rank owns a draw and the donor never writes its request slots
-        return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+        return mp_fail_degenerate();
     if ((flags & 1u) && h->ow_last_cap) {
         // a pair of ranks exchanges more than `capacity` rows (every rank reaches this verdict from the same counts): nothing
         // is committed; the entries stay queued, the caller repeats the expand with exact sizes (capacity 0)
@@ -2080,8 +1850,7 @@ int32_t mp_pf_shard_owned_commit(mp_pf* h, const double* d_rows, double* log_tot
         if (h->ow_world == 1) {
             *log_total_weight = L_one;
         } else {
-            if (h->h_pub->degenerate)
-                return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+            if (h->h_pub->degenerate) return mp_fail_degenerate();
             *log_total_weight = h->h_pub->L;
         }
     }
@@ -2091,17 +1860,14 @@ int32_t mp_pf_shard_owned_commit(mp_pf* h, const double* d_rows, double* log_tot
 int32_t mp_pf_shard_query_packed(mp_pf* h, const uint64_t* d_tiles_all, int32_t world, double* log_ml, double* ess) {
     if (!h || !d_tiles_all) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     HIPCK(hipSetDevice(h->device));
-    int32_t rc = shard_scratch(h, world, h->sh_cap ? h->sh_cap : 1);
-    if (rc != MP_OK) return rc;
+    MPCK(shard_scratch(h, world, h->sh_cap ? h->sh_cap : 1));
     const int nt_all = h->nt * world;
     hipLaunchKernelGGL(k_unpack_tiles, dim3((nt_all + K3_THREADS - 1) / K3_THREADS), dim3(K3_THREADS), 0, h->stream, (const u64*)d_tiles_all, world, h->nt,
                        h->sh_tm_all, h->sh_tW_all, h->sh_tW2_all);
     hipLaunchKernelGGL(k_finalize_tiles, dim3(1), dim3(K3_THREADS), table_lds(nt_all, K3_THREADS), h->stream, h->sh_tm_all, h->sh_tW_all, h->sh_tW2_all,
                        nt_all, h->S, h->n_global, 1, h->scal);
-    rc = check_launch("k_finalize_tiles");
-    if (rc != MP_OK) return rc;
-    rc = fetch_scalars(h);
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("k_finalize_tiles"));
+    MPCK(fetch_scalars(h));
     if (log_ml) *log_ml = h->h_scal->lml_fresh;
     if (ess) *ess = h->h_scal->ess_fresh;
     return MP_OK;
@@ -2152,18 +1918,16 @@ int32_t mp_pf_time(mp_pf* h, int64_t* out) {
 int32_t mp_pf_run(mp_pf* h, const double* args0, const double* obs, int32_t n_steps, int32_t scheme) {
     if (!h || !obs) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
     if (n_steps < 1) return mp_fail(MP_ERR_CONSTRAINTS, "run needs at least one time step");
-    int32_t rc = mp_pf_init_step(h, args0, obs, 1);
-    if (rc != MP_OK) return rc;
-    rc = mp_pf_resample(h, scheme, nullptr);
-    if (rc != MP_OK) return rc;
+    MPCK(mp_pf_init_step(h, args0, obs, 1));
+    MPCK(mp_pf_resample(h, scheme, nullptr));
     // (the log-weights a step would store are dead here — `resample` zeroes them, particle_filter.rs:114 — and so are the parents of
     // every resample but the last: k_propagate_mt launches leave both out and reproduce them on demand, mp_pf::lazy_pending; round 4 did
     // that for this loop only, by flags that a failing resample left behind)
-    for (int t = 1; t < n_steps && rc == MP_OK; ++t) {
-        rc = mp_pf_step(h, obs + (size_t)t * h->ops->dim_obs, 1);
-        if (rc == MP_OK) rc = mp_pf_resample(h, scheme, nullptr);
+    for (int t = 1; t < n_steps; ++t) {
+        MPCK(mp_pf_step(h, obs + (size_t)t * h->ops->dim_obs, 1));
+        MPCK(mp_pf_resample(h, scheme, nullptr));
     }
-    return rc;
+    return MP_OK;
 }
 
 int32_t mp_pf_synchronize(mp_pf* h) {
@@ -2171,15 +1935,13 @@ int32_t mp_pf_synchronize(mp_pf* h) {
     HIPCK(hipSetDevice(h->device));
     // polling the stream and one host-mapped word: copying the scalars back for their `degenerate` field cost 15 us of every call
     HIPCK(stream_wait(h->stream));
-    if (*(volatile int*)h->h_flag)
-        return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+    if (*(volatile int*)h->h_flag) return mp_fail_degenerate();
     return MP_OK;
 }
 
 int32_t mp_pf_set_timing(mp_pf* h, int32_t enabled) {
     if (!h) return mp_fail(MP_ERR_INVALID_ARG, "null handle");
-    int32_t rc = drain_timing(h);
-    if (rc != MP_OK) return rc;
+    MPCK(drain_timing(h));
     h->timing = enabled != 0;
     for (int f = 0; f < MP_K_COUNT; ++f) {
         h->fam_ms[f] = 0.;
@@ -2190,8 +1952,7 @@ int32_t mp_pf_set_timing(mp_pf* h, int32_t enabled) {
 
 int32_t mp_pf_get_timing(mp_pf* h, int32_t which, double* total_ms, uint64_t* launches) {
     if (!h || which < 0 || which >= MP_K_COUNT) return mp_fail(MP_ERR_INVALID_ARG, "bad argument");
-    int32_t rc = drain_timing(h);
-    if (rc != MP_OK) return rc;
+    MPCK(drain_timing(h));
     if (total_ms) *total_ms = h->fam_ms[which];
     if (launches) *launches = h->fam_launches[which];
     return MP_OK;
@@ -2247,8 +2008,7 @@ int32_t mp_unfold_simulate(const mp_model_desc* model, const double* args0, int3
     if (n == 0 || n > 0xFFFFFFFFull) return mp_fail(MP_ERR_INVALID_ARG, "n must be in [1, 2^32)");
     if (model->kind == MP_MODEL_HMM) return mp_fail(MP_ERR_UNSUPPORTED, "the reference's HMM has no simulate (tests/hmm/model.rs: unimplemented)");
     std::unique_ptr<ModelOps> ops;
-    int32_t rc = make_model(model, ops);
-    if (rc != MP_OK) return rc;
+    MPCK(make_model(model, ops));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         (void)hipGetLastError();
@@ -2290,37 +2050,27 @@ static int32_t importance_run(const mp_model_desc* model, const double* args0, c
     mp_pf* h = nullptr;
     // (the traces themselves — importance.rs:26-27 returns all N of them — are every sample's states at every step: the ancestry
     // record, which without a resample is each slot's own history)
-    int32_t rc = mp_pf_create(model, num_samples, seed, nullptr, trajectories ? MP_PF_RECORD_HISTORY : 0, device, nullptr, &h);
-    if (rc != MP_OK) return rc;
+    MPCK(mp_pf_create(model, num_samples, seed, nullptr, trajectories ? MP_PF_RECORD_HISTORY : 0, device, nullptr, &h));
     struct Guard { mp_pf* h; ~Guard() { mp_pf_destroy(h); } } guard{h};
     // importance_sampling: N x generate(model_args, constraints) over all n_steps constraints (importance.rs:18-20)
-    rc = mp_pf_init_step(h, args0, obs, n_steps);
-    if (rc != MP_OK) return rc;
-    rc = ensure_rows(h);
-    if (rc != MP_OK) return rc;
+    MPCK(mp_pf_init_step(h, args0, obs, n_steps));
+    MPCK(ensure_rows(h));
     hipLaunchKernelGGL(k_finalize_tiles, dim3(1), dim3(K3_THREADS), table_lds(h->nt, K3_THREADS), h->stream, h->tile_m, h->tile_W, h->tile_W2, h->nt,
                        h->S, h->n, 2, h->scal);
-    rc = check_launch("k_finalize_tiles");
-    if (rc != MP_OK) return rc;
-    rc = fetch_scalars(h);
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("k_finalize_tiles"));
+    MPCK(fetch_scalars(h));
     if (log_ml_estimate) *log_ml_estimate = h->h_scal->lml_fresh;
     if (log_normalized_weights) {
         double* tmp = h->aos;  // n doubles of scratch (dim_state >= 1)
         hipLaunchKernelGGL(k_sub_scalar, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->logw, &h->scal->L, h->n, tmp);
-        rc = check_launch("k_sub_scalar");
-        if (rc != MP_OK) return rc;
+        MPCK(check_launch("k_sub_scalar"));
         HIPCK(hipMemcpyAsync(log_normalized_weights, tmp, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
         HIPCK(hipStreamSynchronize(h->stream));
     }
-    if (final_states) {
-        rc = mp_pf_read_state(h, final_states);
-        if (rc != MP_OK) return rc;
-    }
+    if (final_states) MPCK(mp_pf_read_state(h, final_states));
     if (trajectories) {
         int32_t t_steps = 0;
-        rc = mp_pf_read_trajectories(h, 0, num_samples, trajectories, &t_steps);
-        if (rc != MP_OK) return rc;
+        MPCK(mp_pf_read_trajectories(h, 0, num_samples, trajectories, &t_steps));
     }
     if (resampled_indices && num_ret_samples > 0) {
         // importance_resampling: M categorical draws over exp(lnw) (importance.rs:44-47), slot j of DOM_IS
@@ -2331,7 +2081,7 @@ static int32_t importance_run(const mp_model_desc* model, const double* args0, c
                            h->n_global, (u64)0, (uint32_t)MP_DOM_IS, (uint32_t)h->seed, (uint32_t)(h->seed >> 32), 0u, h->S, h->ops->dim_state, h->cx,
                            h->guide, h->tile_m, h->tile_W, h->tile_W2, h->nt, (const double*)nullptr, (double*)nullptr, d_idx.get(), (double*)nullptr,
                            (mp_dev_scalars*)nullptr);
-        rc = check_launch("k_resample_gather(IS)");
+        const int32_t rc = check_launch("k_resample_gather(IS)");   // (reported after the stream has drained)
         std::vector<uint32_t> idx(num_ret_samples);
         hipError_t e1 = hipMemcpyAsync(idx.data(), d_idx, sizeof(uint32_t) * num_ret_samples, hipMemcpyDeviceToHost, h->stream);
         hipError_t e2 = hipStreamSynchronize(h->stream);
@@ -2383,8 +2133,7 @@ int32_t mp_is_finish_device(const double* d_logw, uint64_t n, uint64_t num_ret, 
     HIPCK(mp_hipMalloc(b.tiles, 3 * (size_t)nt));
     HIPCK(mp_hipMalloc(b.scal, 1));
     HIPCK(hipMemsetAsync(b.scal, 0, sizeof(mp_dev_scalars), st));
-    double* tile_m = reinterpret_cast<double*>(b.tiles.get());
-    u64 *tile_W = b.tiles + nt, *tile_W2 = b.tiles + 2 * (size_t)nt;
+    const auto [tile_m, tile_W, tile_W2] = tile_views(b.tiles, nt);
     const size_t lds = table_lds(nt, K3_THREADS);
     if (lds > 48 * 1024) {
         HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_finalize_tiles), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2395,18 +2144,16 @@ int32_t mp_is_finish_device(const double* d_logw, uint64_t n, uint64_t num_ret, 
     hipLaunchKernelGGL(k_normalize_tiles, dim3(nt), dim3(TILE_THREADS), 0, st, d_logw, d_logw /* x0: the rows' second halves are not read here */, 1, (u64)n, b.cx,
                        b.guide, tile_m, tile_W, tile_W2, tab);
     hipLaunchKernelGGL(k_finalize_tiles, dim3(1), dim3(K3_THREADS), lds, st, tile_m, tile_W, tile_W2, nt, S, (u64)n, 2, b.scal);
-    int32_t rc = check_launch("importance sampling: normalisation");
-    if (rc != MP_OK) return rc;
+    MPCK(check_launch("importance sampling: normalisation"));
     mp_dev_scalars hs;
     HIPCK(hipMemcpyAsync(&hs, b.scal, sizeof(hs), hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
-    if (hs.degenerate) return mp_fail(MP_ERR_DEGENERATE, "all log-weights are -inf: normalized weights are NaN (categorical.rs:23 assert in the reference)");
+    if (hs.degenerate) return mp_fail_degenerate();
     if (log_ml_estimate) *log_ml_estimate = hs.lml_fresh;
     if (log_normalized_weights) {
         HIPCK(mp_hipMalloc(b.tmp, n));
         hipLaunchKernelGGL(k_sub_scalar, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_logw, &b.scal->L, (u64)n, b.tmp);
-        rc = check_launch("k_sub_scalar");
-        if (rc != MP_OK) return rc;
+        MPCK(check_launch("k_sub_scalar"));
         HIPCK(hipMemcpyAsync(log_normalized_weights, b.tmp, sizeof(double) * n, hipMemcpyDeviceToHost, st));
         HIPCK(hipStreamSynchronize(st));
     }
@@ -2416,8 +2163,7 @@ int32_t mp_is_finish_device(const double* d_logw, uint64_t n, uint64_t num_ret, 
         hipLaunchKernelGGL(k_resample_gather<0>, dim3(grid), dim3(KG_THREADS), lds, st, (u64)n, (u64)num_ret, (u64)n, (u64)0, (uint32_t)MP_DOM_IS, (uint32_t)seed,
                            (uint32_t)(seed >> 32), 0u, S, 1, b.cx, b.guide, tile_m, tile_W, tile_W2, nt, (const double*)nullptr, (double*)nullptr, b.idx,
                            (double*)nullptr, (mp_dev_scalars*)nullptr);
-        rc = check_launch("k_resample_gather(IS)");
-        if (rc != MP_OK) return rc;
+        MPCK(check_launch("k_resample_gather(IS)"));
         std::vector<uint32_t> idx(num_ret);
         HIPCK(hipMemcpyAsync(idx.data(), b.idx, sizeof(uint32_t) * num_ret, hipMemcpyDeviceToHost, st));
         HIPCK(hipStreamSynchronize(st));

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mp_dists.h"
+#include "mp_err.h"
 #include "mp_hip_own.h"
 #include "mp_linalg.h"
 
@@ -128,25 +129,20 @@ __global__ void k_probe_mfma_f64(const double* A, const double* B, const double*
     for (int r = 0; r < 4; ++r) D[((l >> 4) + 4 * r) * 16 + (l & 15)] = d[r];
 }
 
-#define PCK(call)                                                              \
-    do {                                                                       \
-        if ((call) != hipSuccess) return MP_ERR_HIP;                           \
-    } while (0)
-
 extern "C" {
 
 int32_t mp_probe_math(int32_t op, const double* a, const double* b, const double* c, int64_t n, double* out, int32_t device) {
     if (op < MP_PROBE_EXP || op > MP_PROBE_ATAN2 || !a || !out || n < 1) return MP_ERR_INVALID_ARG;
     mp_dev<double> da, db, dc, dout;
     const size_t bytes = sizeof(double) * (size_t)n;
-    PCK(hipSetDevice(device));
-    PCK(mp_hipMalloc(da, bytes / sizeof(double))); PCK(mp_hipMalloc(db, bytes / sizeof(double))); PCK(mp_hipMalloc(dc, bytes / sizeof(double))); PCK(mp_hipMalloc(dout, bytes / sizeof(double)));
-    PCK(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
-    if (b) PCK(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice)); else PCK(hipMemset(db, 0, bytes));
-    if (c) PCK(hipMemcpy(dc, c, bytes, hipMemcpyHostToDevice)); else PCK(hipMemset(dc, 0, bytes));
+    HIPCK(hipSetDevice(device));
+    HIPCK(mp_hipMalloc(da, bytes / sizeof(double))); HIPCK(mp_hipMalloc(db, bytes / sizeof(double))); HIPCK(mp_hipMalloc(dc, bytes / sizeof(double))); HIPCK(mp_hipMalloc(dout, bytes / sizeof(double)));
+    HIPCK(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
+    if (b) HIPCK(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice)); else HIPCK(hipMemset(db, 0, bytes));
+    if (c) HIPCK(hipMemcpy(dc, c, bytes, hipMemcpyHostToDevice)); else HIPCK(hipMemset(dc, 0, bytes));
     hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, da, db, dc, (long long)n, dout);
-    PCK(hipGetLastError());
-    PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return MP_OK;
 }
 
@@ -154,12 +150,12 @@ int32_t mp_probe_normal_sample(uint64_t seed, uint32_t slot0, uint32_t step, uin
                                int64_t n, double* out, int32_t device) {
     mp_dev<double> dout;
     const size_t bytes = sizeof(double) * (size_t)n;
-    PCK(hipSetDevice(device));
-    PCK(mp_hipMalloc(dout, bytes / sizeof(double)));
+    HIPCK(hipSetDevice(device));
+    HIPCK(mp_hipMalloc(dout, bytes / sizeof(double)));
     hipLaunchKernelGGL(k_probe_normal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), slot0, step,
                        domain, site, mu, sd, (long long)n, dout);
-    PCK(hipGetLastError());
-    PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return MP_OK;
 }
 
@@ -167,12 +163,12 @@ int32_t mp_probe_u01(uint64_t seed, uint32_t slot0, uint32_t step, uint32_t doma
                      double* out, int32_t device) {
     mp_dev<double> dout;
     const size_t bytes = sizeof(double) * 2 * (size_t)n;
-    PCK(hipSetDevice(device));
-    PCK(mp_hipMalloc(dout, bytes / sizeof(double)));
+    HIPCK(hipSetDevice(device));
+    HIPCK(mp_hipMalloc(dout, bytes / sizeof(double)));
     hipLaunchKernelGGL(k_probe_u01, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), slot0, step,
                        domain, site, attempt, (long long)n, dout);
-    PCK(hipGetLastError());
-    PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return MP_OK;
 }
 
@@ -183,25 +179,25 @@ int32_t mp_probe_mvnormal(int32_t k, int32_t chain, const double* x, const doubl
     std::vector<double> inv, T;
     const double det = mp_host_det(c, k);
     mp_dev<double> dx, dmu, dm, dout;
-    PCK(hipSetDevice(device));
-    PCK(mp_hipMalloc(dmu, k)); PCK(mp_hipMalloc(dm, (size_t)k * k)); PCK(mp_hipMalloc(dout, (size_t)n * k));
-    PCK(hipMemcpy(dmu, mu, sizeof(double) * k, hipMemcpyHostToDevice));
+    HIPCK(hipSetDevice(device));
+    HIPCK(mp_hipMalloc(dmu, k)); HIPCK(mp_hipMalloc(dm, (size_t)k * k)); HIPCK(mp_hipMalloc(dout, (size_t)n * k));
+    HIPCK(hipMemcpy(dmu, mu, sizeof(double) * k, hipMemcpyHostToDevice));
     if (logpdf_out) {
         if (!x || !mp_host_inverse(c, k, inv)) return MP_ERR_INVALID_ARG;   // try_inverse().unwrap() panics (mvnormal.rs:18)
-        PCK(mp_hipMalloc(dx, (size_t)n * k));
-        PCK(hipMemcpy(dx, x, sizeof(double) * (size_t)n * k, hipMemcpyHostToDevice));
-        PCK(hipMemcpy(dm, inv.data(), sizeof(double) * k * k, hipMemcpyHostToDevice));
+        HIPCK(mp_hipMalloc(dx, (size_t)n * k));
+        HIPCK(hipMemcpy(dx, x, sizeof(double) * (size_t)n * k, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(dm, inv.data(), sizeof(double) * k * k, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_probe_mvnormal_logpdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, k, chain, dx, dmu, dm, mp_log(det), (long long)n, dout);
-        PCK(hipGetLastError());
-        PCK(hipMemcpy(logpdf_out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpy(logpdf_out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     }
     if (sample_out) {
         mp_host_mvnormal_transform(c, k, T);   // Cholesky factor, or the eigen form when there is none (mvnormal.rs:26-34)
-        PCK(hipMemcpy(dm, T.data(), sizeof(double) * k * k, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(dm, T.data(), sizeof(double) * k * k, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_probe_mvnormal_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, k, chain, (uint32_t)seed, (uint32_t)(seed >> 32), slot0, step,
                            domain, site, dmu, dm, (long long)n, dout);
-        PCK(hipGetLastError());
-        PCK(hipMemcpy(sample_out, dout, sizeof(double) * (size_t)n * k, hipMemcpyDeviceToHost));
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpy(sample_out, dout, sizeof(double) * (size_t)n * k, hipMemcpyDeviceToHost));
     }
     return MP_OK;
 }
@@ -213,28 +209,28 @@ int32_t mp_probe_dist(int32_t dist, int32_t op, const double* x, const double* p
         return MP_ERR_INVALID_ARG;
     mp_dev<double> dx, dp0, dp1, dout;
     const size_t bytes = sizeof(double) * (size_t)n;
-    PCK(hipSetDevice(device));
-    PCK(mp_hipMalloc(dout, bytes / sizeof(double)));
-    if (op == 0) { PCK(mp_hipMalloc(dx, bytes / sizeof(double))); PCK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice)); }
-    if (p0) { PCK(mp_hipMalloc(dp0, bytes / sizeof(double))); PCK(hipMemcpy(dp0, p0, bytes, hipMemcpyHostToDevice)); }
-    if (p1) { PCK(mp_hipMalloc(dp1, bytes / sizeof(double))); PCK(hipMemcpy(dp1, p1, bytes, hipMemcpyHostToDevice)); }
+    HIPCK(hipSetDevice(device));
+    HIPCK(mp_hipMalloc(dout, bytes / sizeof(double)));
+    if (op == 0) { HIPCK(mp_hipMalloc(dx, bytes / sizeof(double))); HIPCK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice)); }
+    if (p0) { HIPCK(mp_hipMalloc(dp0, bytes / sizeof(double))); HIPCK(hipMemcpy(dp0, p0, bytes, hipMemcpyHostToDevice)); }
+    if (p1) { HIPCK(mp_hipMalloc(dp1, bytes / sizeof(double))); HIPCK(hipMemcpy(dp1, p1, bytes, hipMemcpyHostToDevice)); }
     hipLaunchKernelGGL(k_probe_dist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)dist, (int)op, dx, dp0, dp1, (long long)n,
                        (uint32_t)seed, (uint32_t)(seed >> 32), slot0, step, domain, site, dout);
-    PCK(hipGetLastError());
-    PCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return MP_OK;
 }
 
 int32_t mp_probe_mfma_f64(const double* A16x4, const double* B4x16, const double* C16x16, double* D16x16, int32_t device) {
     mp_dev<double> da, db, dc, dd;
-    PCK(hipSetDevice(device));
-    PCK(mp_hipMalloc(da, 64)); PCK(mp_hipMalloc(db, 64)); PCK(mp_hipMalloc(dc, 256)); PCK(mp_hipMalloc(dd, 256));
-    PCK(hipMemcpy(da, A16x4, sizeof(double) * 64, hipMemcpyHostToDevice));
-    PCK(hipMemcpy(db, B4x16, sizeof(double) * 64, hipMemcpyHostToDevice));
-    PCK(hipMemcpy(dc, C16x16, sizeof(double) * 256, hipMemcpyHostToDevice));
+    HIPCK(hipSetDevice(device));
+    HIPCK(mp_hipMalloc(da, 64)); HIPCK(mp_hipMalloc(db, 64)); HIPCK(mp_hipMalloc(dc, 256)); HIPCK(mp_hipMalloc(dd, 256));
+    HIPCK(hipMemcpy(da, A16x4, sizeof(double) * 64, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(db, B4x16, sizeof(double) * 64, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(dc, C16x16, sizeof(double) * 256, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_probe_mfma_f64, dim3(1), dim3(64), 0, 0, da, db, dc, dd);
-    PCK(hipGetLastError());
-    PCK(hipMemcpy(D16x16, dd, sizeof(double) * 256, hipMemcpyDeviceToHost));
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpy(D16x16, dd, sizeof(double) * 256, hipMemcpyDeviceToHost));
     return MP_OK;
 }
 

@@ -53,8 +53,7 @@ static int32_t shard_native_init(mp_pf* h, int world) {
     const int d = h->ops->dim_state;
     HIPCK(mp_hipMalloc(s->tiles, 3 * h->nt));
     HIPCK(mp_hipMalloc(s->tiles_all, 3 * h->nt * (size_t)world));
-    int32_t rc = mp_pf_shard_bind_tiles(h, s->tiles);   // the filter keeps its tiles where the all-gather reads them
-    if (rc != MP_OK) return rc;
+    MPCK(mp_pf_shard_bind_tiles(h, s->tiles));   // the filter keeps its tiles where the all-gather reads them
     // surplus rows per pair of ranks in the equal-split exchange: the surplus of a rank is the spread of a Binomial(N, ~1/world)
     // count plus the imbalance of the shard masses, both O(sqrt n): sd ~ sqrt(2 n) = 1400 rows at 2^20 particles per rank, so
     // 8192 rows per pair is ~6 sigma; a pair that needs more falls back once (exact sizes) and the capacity doubles.
@@ -68,8 +67,7 @@ static int32_t shard_native_init(mp_pf* h, int world) {
     // (one host round trip per resample, a few percent of such a step).
     if (s->fixed && !s->cap_forced && (uint64_t)world * cap * (d + 1) * 8 > s->fixed_max_bytes) s->fixed = false;
     if (s->fixed) {
-        rc = shard_native_alloc_fixed(h, s, cap);
-        if (rc != MP_OK) return rc;
+        MPCK(shard_native_alloc_fixed(h, s, cap));
     } else {
         s->cap = cap;
     }
@@ -106,21 +104,20 @@ static void shard_owned_plan(const uint64_t* counts, int world, uint64_t n, std:
 int32_t mp_pf_shard_resample(mp_pf* h, const mp_transport* t, int32_t world, int32_t rank, int32_t scheme, int32_t force_collectives,
                              double* log_total_weight) {
     if (!h) return mp_fail(MP_ERR_INVALID_ARG, "null handle");
-    if (world < 1 || world > SH_MAX_WORLD || rank < 0 || rank >= world) return mp_fail(MP_ERR_INVALID_ARG, "1 <= world <= 64, 0 <= rank < world");
+    MPCK(check_world_rank(world, rank));
     const bool solo = world == 1 && !force_collectives;
     if (!solo && (!t || !t->all_gather || !t->all_to_all)) return mp_fail(MP_ERR_INVALID_ARG, "a world of more than one needs a transport");
     HIPCK(hipSetDevice(h->device));
     if (!h->native || h->native->world != world) {
         h->native.reset();
-        int32_t rci = shard_native_init(h, world);
-        if (rci != MP_OK) return rci;
+        MPCK(shard_native_init(h, world));
     }
     mp_shard_native_state* s = h->native.get();
     const int d = h->ops->dim_state;
     const size_t row_b = sizeof(double) * (size_t)(d + 1);
-    int32_t rc = mp_pf_shard_tiles_packed(h, s->tiles);
-    if (rc != MP_OK) return rc;
+    MPCK(mp_pf_shard_tiles_packed(h, s->tiles));
     const uint64_t* tiles_all = s->tiles;
+    int32_t rc = MP_OK;   // (the transport's statuses, and the capacity verdict of the equal-split commit)
     if (!solo) {
         rc = t->all_gather(t->ctx, s->tiles, s->tiles_all, sizeof(uint64_t) * 3 * (uint64_t)h->nt, (void*)h->stream);
         if (rc != MP_OK) return mp_fail(rc, "sharded resample: all-gather of the tiles failed");
@@ -133,8 +130,7 @@ int32_t mp_pf_shard_resample(mp_pf* h, const mp_transport* t, int32_t world, int
         // 2 collectives, 3 phases, one host wait (for the plan's verdict word, while the rows are written and travel)
         double* rows = s->rows[s->flip];
         s->flip ^= 1;
-        rc = mp_pf_shard_owned_count_expand(h, scheme, tiles_all, world, rank, s->cap, s->send, rows, (uint64_t)world * s->cap);
-        if (rc != MP_OK) return rc;
+        MPCK(mp_pf_shard_owned_count_expand(h, scheme, tiles_all, world, rank, s->cap, s->send, rows, (uint64_t)world * s->cap));
         if (!solo) {
             for (int q = 0; q < world; ++q) { so[q] = ro[q] = (uint64_t)q * s->cap * row_b; sb[q] = rb[q] = s->cap * row_b; }
             rc = t->all_to_all(t->ctx, s->send, so.data(), sb.data(), rows, ro.data(), rb.data(), world, (void*)h->stream);
@@ -157,8 +153,7 @@ int32_t mp_pf_shard_resample(mp_pf* h, const mp_transport* t, int32_t world, int
         if (rc != MP_ERR_CAPACITY) return rc == MP_OK ? mp_fail(MP_ERR_STATE, "owner-keeps exchange: the capacity verdict changed between two reads") : rc;
         need_exact = true;
     } else {
-        rc = mp_pf_shard_owned_count(h, scheme, tiles_all, world, rank, 0, counts);
-        if (rc != MP_OK) return rc;
+        MPCK(mp_pf_shard_owned_count(h, scheme, tiles_all, world, rank, 0, counts));
     }
     (void)need_exact;
     s->have_counts = true;
@@ -177,20 +172,16 @@ int32_t mp_pf_shard_resample(mp_pf* h, const mp_transport* t, int32_t world, int
     const uint64_t keep_rows = d == 1 ? h->n : 0;
     const int k = s->xflip;
     s->xflip ^= 1;
-    rc = shard_native_grow(s->xsend[k], &s->xsend_rows[k], std::max<uint64_t>(n_send, 1), d + 1);
-    if (rc != MP_OK) return rc;
-    rc = shard_native_grow(s->xrows[k], &s->xrows_rows[k], std::max<uint64_t>(n_recv + keep_rows, 1), d + 1);
-    if (rc != MP_OK) return rc;
-    rc = mp_pf_shard_owned_expand(h, world, rank, 0, s->xsend[k], s->xrows[k], n_recv);
-    if (rc != MP_OK) return rc;
+    MPCK(shard_native_grow(s->xsend[k], &s->xsend_rows[k], std::max<uint64_t>(n_send, 1), d + 1));
+    MPCK(shard_native_grow(s->xrows[k], &s->xrows_rows[k], std::max<uint64_t>(n_recv + keep_rows, 1), d + 1));
+    MPCK(mp_pf_shard_owned_expand(h, world, rank, 0, s->xsend[k], s->xrows[k], n_recv));
     if (!solo && total > 0) {   // (nobody has a surplus: every rank sees the same counts, so every rank skips the collective)
         rc = t->all_to_all(t->ctx, s->xsend[k], so.data(), sb.data(), s->xrows[k], ro.data(), rb.data(), world, (void*)h->stream);
         if (rc != MP_OK) return mp_fail(rc, "sharded resample: exact-size all-to-all failed");
     } else if (n_recv) {
         HIPCK(hipMemcpyAsync(s->xrows[k], s->xsend[k], n_recv * row_b, hipMemcpyDeviceToDevice, h->stream));   // a world of one with forced exact sizes
     }
-    rc = mp_pf_shard_owned_commit(h, s->xrows[k], log_total_weight, nullptr);
-    if (rc != MP_OK) return rc;
+    MPCK(mp_pf_shard_owned_commit(h, s->xrows[k], log_total_weight, nullptr));
     if (s->fixed && !s->cap_forced && s->cap < h->n) {
         // the next resample can use equal splits again, with room for what this one needed (every rank grows alike)
         uint64_t worst = 0;
@@ -200,8 +191,7 @@ int32_t mp_pf_shard_resample(mp_pf* h, const mp_transport* t, int32_t world, int
             s->fixed = false;
         } else {
             HIPCK(stream_wait(h->stream));   // nothing refers to the old equal-split buffers any more
-            rc = shard_native_alloc_fixed(h, s, grown);
-            if (rc != MP_OK) return rc;
+            MPCK(shard_native_alloc_fixed(h, s, grown));
         }
     }
     return MP_OK;
@@ -225,15 +215,13 @@ int32_t mp_pf_shard_query_native(mp_pf* h, const mp_transport* t, int32_t world,
     HIPCK(hipSetDevice(h->device));
     if (!h->native || h->native->world != world) {
         h->native.reset();
-        int32_t rci = shard_native_init(h, world);
-        if (rci != MP_OK) return rci;
+        MPCK(shard_native_init(h, world));
     }
     mp_shard_native_state* s = h->native.get();
-    int32_t rc = mp_pf_shard_tiles_packed(h, s->tiles);
-    if (rc != MP_OK) return rc;
+    MPCK(mp_pf_shard_tiles_packed(h, s->tiles));
     const uint64_t* tiles_all = s->tiles;
     if (!solo) {
-        rc = t->all_gather(t->ctx, s->tiles, s->tiles_all, sizeof(uint64_t) * 3 * (uint64_t)h->nt, (void*)h->stream);
+        const int32_t rc = t->all_gather(t->ctx, s->tiles, s->tiles_all, sizeof(uint64_t) * 3 * (uint64_t)h->nt, (void*)h->stream);
         if (rc != MP_OK) return mp_fail(rc, "sharded query: all-gather of the tiles failed");
         tiles_all = s->tiles_all;
     }
@@ -348,10 +336,7 @@ int32_t mp_transport_rccl(void* nccl_comm, mp_transport* out) {
 int32_t mp_pf_shard_resample_rccl(mp_pf* h, void* nccl_comm, int32_t world, int32_t rank, int32_t scheme, int32_t force_collectives,
                                   double* log_total_weight) {
     mp_transport t;
-    if (world > 1 || force_collectives) {
-        int32_t rc = mp_transport_rccl(nccl_comm, &t);
-        if (rc != MP_OK) return rc;
-    }
+    if (world > 1 || force_collectives) MPCK(mp_transport_rccl(nccl_comm, &t));
     return mp_pf_shard_resample(h, (world > 1 || force_collectives) ? &t : nullptr, world, rank, scheme, force_collectives, log_total_weight);
 }
 // plain device <-> host copies on the filter's stream, for transports that stage through the host (tests)
