@@ -44,8 +44,9 @@ MP_HD double mp_normal_logpdf_h(double x, double mu, double sd, double ln_sd, do
 // normal.rs:25-26: c = sqrt(-2 ln r / r); u*c*std + mu.
 // The standard deviate z = u*c is the parameter-free part: `u * c * std + mu` evaluates as ((u*c)*std) + mu, so a kernel may
 // produce z anywhere (another lane, another launch) and the model finishes with z*sd + mu — same operations, same order.
-MP_HD double mp_std_normal_from_pair(double u, double r) {
-    const double c = mp_sqrt(-2. * mp_log(r) / r);
+// (SC: mp_log_'s choice of where its constants live, mp_math.h — true in the propagate kernels of the models with few deviates per particle)
+template <bool SC = false> MP_HD double mp_std_normal_from_pair(double u, double r) {
+    const double c = mp_sqrt(-2. * mp_log_<SC>(r) / r);
     return u * c;
 }
 MP_HD double mp_normal_from_pair(double u, double r, double mu, double sd) { return mp_std_normal_from_pair(u, r) * sd + mu; }

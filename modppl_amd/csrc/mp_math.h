@@ -37,6 +37,54 @@ MP_HD double mp_u2f(uint64_t u) { return __builtin_bit_cast(double, u); }
 #define MP_PI 3.141592653589793
 
 // ---------------------------------------------------------------------------------------
+// One fp64 operation with a compile-time constant C as an operand.  gfx950 has no 64-bit literal operand, and left to itself the
+// compiler puts every such constant into a VGPR pair first (two v_mov_b32 in front of each Horner step: three VALU issues for one
+// operation).  On the device the constant goes through an "s" constraint instead: two s_mov_b32 on the scalar unit (still
+// rematerialisable: no live range grows) and ONE v_fma_f64 / v_add_f64 / v_mul_f64 with an SGPR-pair operand — the same IEEE
+// operation on the same operands, so the same bits.  One scalar operand per instruction is what VOP3 allows here; a and b are
+// run-time values.  On the host these are fma, + and * themselves.
+//   mp_fma_c(a, b, C) = fma(a, b, C)     mp_fnma_c(a, C, c) = fma(-a, C, c)     mp_add_c(a, C) = C + a     mp_mul_c(a, C) = a * C
+// C MUST be a literal (or a constexpr double): an "s" operand is one value per wave, so for a C that differs from lane to lane the
+// compiler would take lane 0's (v_readfirstlane) for all 64 without a word.  The language gives no way to demand that of a double
+// argument in C++17; every use is a named constant a few lines above it, and a new one has to be as well.  The results are ordinary
+// VGPR values; the compiler pads the wait states between one of these and a DPP instruction of its own that reads the result.
+// ---------------------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ double mp_fma_c(double a, double b, double C) {
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(C));
+    return r;
+}
+__device__ __forceinline__ double mp_fnma_c(double a, double C, double c) {
+    double r;
+    asm("v_fma_f64 %0, -%1, %2, %3" : "=v"(r) : "v"(a), "s"(C), "v"(c));
+    return r;
+}
+__device__ __forceinline__ double mp_add_c(double a, double C) {
+    double r;
+    asm("v_add_f64 %0, %1, %2" : "=v"(r) : "s"(C), "v"(a));
+    return r;
+}
+__device__ __forceinline__ double mp_mul_c(double a, double C) {
+    double r;
+    asm("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(C));
+    return r;
+}
+#else
+MP_HD double mp_fma_c(double a, double b, double C) { return fma(a, b, C); }
+MP_HD double mp_fnma_c(double a, double C, double c) { return fma(-a, C, c); }
+MP_HD double mp_add_c(double a, double C) { return C + a; }
+MP_HD double mp_mul_c(double a, double C) { return a * C; }
+#endif
+// ... or, SC = false, the plain expression (the compiler's own choice of registers).  Same operation either way.  The scalar form
+// is for the hot per-particle chains only (mp_exp, mp_exp_nonpos, the logarithm of the narrow models' deviates).  mp_log's other
+// uses — the one-thread folds of the tile scalars, model constants, the wide models' sixteen deviates per particle — keep the plain
+// form: with inline assembly in them the compiler compiled k_propagate<mp_lgssm_band<16>, 512> into half as many instructions but
+// with three times the SGPR spills (v_writelane 30 -> 93, v_readlane 62 -> 204), and it ran 438 -> 491 us per step.
+template <bool SC> MP_HD double mp_add_cs(double a, double C) { if constexpr (SC) return mp_add_c(a, C); else return C + a; }
+template <bool SC> MP_HD double mp_mul_cs(double a, double C) { if constexpr (SC) return mp_mul_c(a, C); else return a * C; }
+
+// ---------------------------------------------------------------------------------------
 // x / d with the reciprocal r = RN(1 / d) hoisted (d is a model constant: an observation noise, a drift width): the bits of the
 // IEEE division without the division.  q0 = RN(x r) is within two ulps of x / d; one residual correction (rem = x - q0 d, exact
 // in an fma) makes it faithful, a second one correctly rounded (Markstein's theorem: correct rounding from a faithful quotient
@@ -79,21 +127,21 @@ MP_HD double mp_exp(double x) {
     const double INV_LN2 = 1.4426950408889634;
     const double LN2_HI = 6.93147180369123816490e-01;  // 0x3FE62E42FEE00000
     const double LN2_LO = 1.90821492927058770002e-10;  // 0x3DEA39EF35793C76
-    const double kf = rint(x * INV_LN2);
-    double r = fma(-kf, LN2_HI, x);
-    r = fma(-kf, LN2_LO, r);
+    const double kf = rint(mp_mul_c(x, INV_LN2));
+    double r = mp_fnma_c(kf, LN2_HI, x);
+    r = mp_fnma_c(kf, LN2_LO, r);
     // P(r) = sum_{n=2..13} r^(n-2)/n!
     double p = 1.6059043836821613e-10;   // 1/13!
-    p = fma(p, r, 2.08767569878681e-09); // 1/12!
-    p = fma(p, r, 2.505210838544172e-08);   // 1/11!
-    p = fma(p, r, 2.755731922398589e-07);   // 1/10!
-    p = fma(p, r, 2.7557319223985893e-06);  // 1/9!
-    p = fma(p, r, 2.48015873015873e-05);    // 1/8!
-    p = fma(p, r, 1.984126984126984e-04);   // 1/7!
-    p = fma(p, r, 1.388888888888889e-03);   // 1/6!
-    p = fma(p, r, 8.333333333333333e-03);   // 1/5!
-    p = fma(p, r, 4.1666666666666664e-02);  // 1/4!
-    p = fma(p, r, 1.6666666666666666e-01);  // 1/3!
+    p = mp_fma_c(p, r, 2.08767569878681e-09); // 1/12!
+    p = mp_fma_c(p, r, 2.505210838544172e-08);   // 1/11!
+    p = mp_fma_c(p, r, 2.755731922398589e-07);   // 1/10!
+    p = mp_fma_c(p, r, 2.7557319223985893e-06);  // 1/9!
+    p = mp_fma_c(p, r, 2.48015873015873e-05);    // 1/8!
+    p = mp_fma_c(p, r, 1.984126984126984e-04);   // 1/7!
+    p = mp_fma_c(p, r, 1.388888888888889e-03);   // 1/6!
+    p = mp_fma_c(p, r, 8.333333333333333e-03);   // 1/5!
+    p = mp_fma_c(p, r, 4.1666666666666664e-02);  // 1/4!
+    p = mp_fma_c(p, r, 1.6666666666666666e-01);  // 1/3!
     p = fma(p, r, 0.5);
     const double y = 1.0 + fma(r * r, p, r);  // in [0.70, 1.42]
     const int k = (int)kf;
@@ -110,7 +158,8 @@ MP_HD double mp_exp(double x) {
 // ---------------------------------------------------------------------------------------
 // log
 // ---------------------------------------------------------------------------------------
-MP_HD double mp_log(double x) {
+// SC: the constants as scalar operands (mp_add_c / mp_mul_c above) or left to the compiler; mp_log(x) = mp_log_<false>(x)
+template <bool SC> MP_HD double mp_log_(double x) {
     const double LN2_HI = 6.93147180369123816490e-01;
     const double LN2_LO = 1.90821492927058770002e-10;
     const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01,
@@ -143,12 +192,13 @@ MP_HD double mp_log(double x) {
     const double s = f / (2.0 + f);
     const double z = s * s;
     const double w = z * z;
-    const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
-    const double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
+    const double t1 = w * mp_add_cs<SC>(w * mp_add_cs<SC>(mp_mul_cs<SC>(w, Lg6), Lg4), Lg2);                         // w (Lg2 + w (Lg4 + w Lg6))
+    const double t2 = z * mp_add_cs<SC>(w * mp_add_cs<SC>(w * mp_add_cs<SC>(mp_mul_cs<SC>(w, Lg7), Lg5), Lg3), Lg1);  // z (Lg1 + w (Lg3 + w (Lg5 + w Lg7)))
     const double R = t2 + t1;
     const double dk = (double)k;
-    return s * (hfsq + R) + dk * LN2_LO - hfsq + f + dk * LN2_HI;
+    return s * (hfsq + R) + mp_mul_cs<SC>(dk, LN2_LO) - hfsq + f + mp_mul_cs<SC>(dk, LN2_HI);
 }
+MP_HD double mp_log(double x) { return mp_log_<false>(x); }
 
 // sqrt and division are IEEE-754 correctly rounded for fp64 both in SSE2 and in the gfx950
 // expansion hipcc emits without fast-math (checked bit-for-bit in tests/test_gpu_math.py).

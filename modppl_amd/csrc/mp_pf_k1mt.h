@@ -297,7 +297,7 @@ __device__ __forceinline__ void mt_deviates(const Model& model, int ns, const mp
         }
     }
 #pragma unroll
-    for (int q = 0; q < M; ++q) z[q] = mp_std_normal_from_pair(pu[q], pr[q]);
+    for (int q = 0; q < M; ++q) z[q] = mp_std_normal_from_pair<true>(pu[q], pr[q]);
 }
 
 #ifndef MP_MT_WALK_BARRIER
@@ -359,14 +359,12 @@ __device__ __forceinline__ void mt_norm_compute(const double (&lw)[2], u64 n, u6
     double m = MP_NEG_INF;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-        if (base + j < n) m = fmax(m, lw[j]);
+        if (base + j < n) m = mp_max_q(m, lw[j]);
     m = wave_max(m);
     if (lane == 0) L.s_red[wave] = m;
     reinterpret_cast<uint32_t*>(s_guide)[tid] = 0u;   // 1024 threads x 4 B = the whole guide
     mt_lds_barrier();
-    m = L.s_red[0];
-#pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) m = fmax(m, L.s_red[w]);
+    m = xwave_max<THREADS / 64>(L.s_red, lane);
     const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
     u64 c[2];
     u64 run = 0, run2 = 0;
@@ -383,15 +381,8 @@ __device__ __forceinline__ void mt_norm_compute(const double (&lw)[2], u64 n, u6
     if (lane == 63) L.s_wsum[wave] = incl;
     if (lane == 0) L.s_wsum2[wave] = wtot2;
     mt_lds_barrier();
-    u64 woff = 0, W = 0;
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-    for (int k = 0; k < THREADS / 64; ++k) {
-        const u64 vv = L.s_wsum[k];
-        const u64 v = ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(vv >> 32)) << 32) | (u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)vv);
-        if (k < wave_s) woff += v;
-        W += v;
-    }
+    u64 woff, W;
+    xwave_prefix<THREADS / 64>(L.s_wsum, lane, wave, woff, W);
     const u64 off = woff + (incl - run);
     u64 t2 = 0;
     if (tid == 0) {
@@ -499,7 +490,7 @@ __device__ __forceinline__ void mt_peek_tail(const mp_k1mt& a, int nt) {
     __syncthreads();
     m = s_red[0];
 #pragma unroll 1
-    for (int w = 1; w < 16; ++w) m = fmax(m, s_red[w]);
+    for (int w = 1; w < 16; ++w) m = mp_max_q(m, s_red[w]);
     const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
     const double sc = mp_u2f((u64)(1023 + a.S - FIX_BITS) << 52);  // 2^(S-51)
     u64 q = 0, q2 = 0;
@@ -591,9 +582,7 @@ __global__ __launch_bounds__(1024) void k_propagate_mt(const double* __restrict_
         s_l1_tot2[wave1] = 0ull;
     }
     __syncthreads();
-    double m = s_l1_red[0];
-#pragma unroll
-    for (int w = 1; w < NWV; ++w) m = fmax(m, s_l1_red[w]);
+    const double m = xwave_max<NWV>(s_l1_red, lane1);
     u64 incl = 0ull, Tq = 0ull;
     if (wave_has) {
         const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
@@ -611,14 +600,9 @@ __global__ __launch_bounds__(1024) void k_propagate_mt(const double* __restrict_
     __syncthreads();
     {
         u64 Qall = 0;
-        if (wave_has || (blockIdx.x == 0 && threadIdx.x == 0)) {
-            u64 woff = 0;
-#pragma unroll
-            for (int k = 0; k < NWV; ++k) {
-                const u64 tk = s_l1_tot[k];
-                if (k < wave1) woff += tk;
-                Qall += tk;
-            }
+        if (wave_has || wave1 == 0) {   // (wave-uniform; wave 0 for the fold below)
+            u64 woff;
+            xwave_prefix<NWV>(s_l1_tot, lane1, wave1, woff, Qall);
             if (have_tb) {
                 s_incl[tb] = woff + incl;
                 s_W[tb] = Wb;

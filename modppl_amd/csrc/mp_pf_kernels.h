@@ -186,28 +186,93 @@ __device__ __forceinline__ u64 mp_dpp_u64(u64 old, u64 v) {
 __device__ __forceinline__ u64 mp_readlane_u64(u64 v, int l) {
     return ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) | (u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
 }
+// One step of a 64-bit scan as the carry-chained pair of 32-bit adds, each taking the other lane's half straight from its DPP
+// source: v += (lane's source ? its v : 0) in two VALU instructions (a 64-bit add of two DPP moves' results came out as five to
+// six).  A lane without a source adds 0 (bound_ctrl) or, in a row that the step's row mask leaves out, is not written at all.
+// (s_nop 1: a DPP source written by the VALU instruction just before needs two wait states, and the compiler does not see into
+// the assembly — neither here nor between two steps.)
+#define MP_SCAN_STEP(DPP)                                                                                                        \
+    asm("s_nop 1\n\tv_add_co_u32_dpp %0, vcc, %0, %0 " DPP "\n\tv_addc_co_u32_dpp %1, vcc, %1, %1, vcc " DPP : "+v"(lo), "+v"(hi) : : "vcc")
 // inclusive scan across the 64 lanes of a wave (lanes without a source add 0)
 __device__ __forceinline__ u64 wave_incl_scan_u64(u64 v, int /*lane*/) {
-    v += mp_dpp_u64<0x111, 0xF, true>(0ull, v);   // row_shr:1
-    v += mp_dpp_u64<0x112, 0xF, true>(0ull, v);   // row_shr:2
-    v += mp_dpp_u64<0x114, 0xF, true>(0ull, v);   // row_shr:4
-    v += mp_dpp_u64<0x118, 0xF, true>(0ull, v);   // row_shr:8
-    v += mp_dpp_u64<0x142, 0xA, false>(0ull, v);  // row_bcast:15 into rows 1 and 3
-    v += mp_dpp_u64<0x143, 0xC, false>(0ull, v);  // row_bcast:31 into rows 2 and 3
-    return v;
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    MP_SCAN_STEP("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    MP_SCAN_STEP("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    MP_SCAN_STEP("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    MP_SCAN_STEP("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    MP_SCAN_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf");   // into rows 1 and 3
+    MP_SCAN_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf");   // into rows 2 and 3
+    return ((u64)hi << 32) | (u64)lo;
 }
+// ... and across the 16 lanes of each row only (the cross-wave combines: one value per wave of the workgroup in lanes 0..15)
+__device__ __forceinline__ u64 row_incl_scan_u64(u64 v) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    MP_SCAN_STEP("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    MP_SCAN_STEP("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    MP_SCAN_STEP("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    MP_SCAN_STEP("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    return ((u64)hi << 32) | (u64)lo;
+}
+#undef MP_SCAN_STEP
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) { return mp_readlane_u64(wave_incl_scan_u64(v, 0), 63); }
-__device__ __forceinline__ double wave_max(double x) {   // lanes without a source keep their own value
-    u64 v = mp_f2u(x);
-#define MP_MAX_STEP(CTRL, MASK) v = mp_f2u(fmax(mp_u2f(v), mp_u2f(mp_dpp_u64<CTRL, MASK, false>(v, v))))
+// The maximum of two values neither of which is a signalling NaN: one v_max_f64.  fmax() has to quiet a signalling NaN, and of a
+// value that comes out of a load, a bit cast or a DPP move the compiler cannot know that it is none, so it puts a v_max_f64 x, x, x
+// in front of the maximum for each such operand.  For a quiet NaN v_max_f64 (IEEE mode) returns the other operand, as fmax does.
+// Why no operand is ever a signalling NaN where this is used: the wave and workgroup maxima run over log-weights and tile maxima,
+// which are results of fp64 arithmetic (the model's density sums, `0. + weight`) or -inf / tile scalars that these kernels wrote
+// from such maxima — an arithmetic instruction never returns a signalling NaN, and no raw caller-supplied bits reach a reduction.
+// That is an invariant of the call sites, not something this function can check: a maximum over bits that did not come out of fp64
+// arithmetic (a caller's buffer, an uninitialised allocation) has to use fmax.
+__device__ __forceinline__ double mp_max_q(double a, double b) {
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// Lanes without a source keep their maximum so far: the DPP moves land in t, whose stale content (this lane's own value at first,
+// then what earlier steps brought in, which v has taken in already) changes nothing.  Two DPP moves and one v_max_f64 per step.
+#define MP_MAX_STEP(CTRL, MASK) t = mp_dpp_u64<CTRL, MASK, false>(t, v); v = mp_f2u(mp_max_q(mp_u2f(v), mp_u2f(t)))
+__device__ __forceinline__ double wave_max(double x) {
+    u64 v = mp_f2u(x), t = v;
     MP_MAX_STEP(0x111, 0xF);
     MP_MAX_STEP(0x112, 0xF);
     MP_MAX_STEP(0x114, 0xF);
     MP_MAX_STEP(0x118, 0xF);
     MP_MAX_STEP(0x142, 0xA);
     MP_MAX_STEP(0x143, 0xC);
-#undef MP_MAX_STEP
     return mp_u2f(mp_readlane_u64(v, 63));
+}
+// ... within each row of 16 lanes: lane 15 of a row holds the row's maximum
+__device__ __forceinline__ double row_max(double x) {
+    u64 v = mp_f2u(x), t = v;
+    MP_MAX_STEP(0x111, 0xF);
+    MP_MAX_STEP(0x112, 0xF);
+    MP_MAX_STEP(0x114, 0xF);
+    MP_MAX_STEP(0x118, 0xF);
+    return mp_u2f(v);
+}
+#undef MP_MAX_STEP
+// The cross-wave combines behind a barrier, for the NW <= 16 per-wave values a workgroup has left in LDS: lane l of every row of
+// 16 reads value l, one row reduction or row scan combines them and v_readlane hands the results to the scalar side — about 20
+// instructions where reading all NW values into every lane and combining them one by one took over a hundred.  Called by WHOLE
+// waves only (wave-uniform conditions): the row operations read their neighbours' registers.  Integer sums and maxima: any order
+// gives the same bits.
+template <int NW>
+__device__ __forceinline__ double xwave_max(const double* s_red, int lane) {
+    static_assert(NW >= 1 && NW <= 16, "one row of 16 lanes holds a workgroup's per-wave values");
+    const int l = lane & 15;
+    const double v = (NW == 16 || l < NW) ? s_red[l] : MP_NEG_INF;
+    return mp_u2f(mp_readlane_u64(mp_f2u(row_max(v)), 15));
+}
+// woff = sum of s_tot[0 .. wave - 1], total = sum of all NW (wave: this wave's index, wave-uniform)
+template <int NW>
+__device__ __forceinline__ void xwave_prefix(const u64* s_tot, int lane, int wave, u64& woff, u64& total) {
+    static_assert(NW >= 1 && NW <= 16, "one row of 16 lanes holds a workgroup's per-wave values");
+    const int l = lane & 15;
+    const u64 pre = row_incl_scan_u64((NW == 16 || l < NW) ? s_tot[l] : 0ull);
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    total = mp_readlane_u64(pre, 15);
+    const u64 before = mp_readlane_u64(pre, wave_s ? wave_s - 1 : 0);
+    woff = wave_s ? before : 0ull;
 }
 __device__ __forceinline__ u64 mp_quantize(double e, double scale) {
     const double r = rint(e * scale);
@@ -307,7 +372,7 @@ __device__ __forceinline__ void build_tile_table_global(const double* tile_m, co
         __syncthreads();
         m = s_tred[0];
 #pragma unroll 1
-        for (int w = 1; w < THREADS / 64; ++w) m = fmax(m, s_tred[w]);
+        for (int w = 1; w < THREADS / 64; ++w) m = mp_max_q(m, s_tred[w]);
         const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
         const double sc = mp_u2f((u64)(1023 + tab.S - FIX_BITS) << 52);  // 2^(S-51)
         const double d = mb - m;
@@ -353,7 +418,7 @@ __device__ __forceinline__ void build_tile_table_global(const double* tile_m, co
     __syncthreads();
     m = s_tred[0];
 #pragma unroll 1
-    for (int w = 1; w < THREADS / 64; ++w) m = fmax(m, s_tred[w]);
+    for (int w = 1; w < THREADS / 64; ++w) m = mp_max_q(m, s_tred[w]);
     const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
     const double sc = mp_u2f((u64)(1023 + tab.S - FIX_BITS) << 52);  // 2^(S-51)
     u64 run = 0, run2 = 0;
@@ -416,20 +481,20 @@ __device__ __forceinline__ double mp_exp_nonpos(double x) {
     const double INV_LN2 = 1.4426950408889634;
     const double LN2_HI = 6.93147180369123816490e-01;
     const double LN2_LO = 1.90821492927058770002e-10;
-    const double kf = rint(x * INV_LN2);
-    double r = fma(-kf, LN2_HI, x);
-    r = fma(-kf, LN2_LO, r);
+    const double kf = rint(mp_mul_c(x, INV_LN2));
+    double r = mp_fnma_c(kf, LN2_HI, x);
+    r = mp_fnma_c(kf, LN2_LO, r);
     double p = 1.6059043836821613e-10;
-    p = fma(p, r, 2.08767569878681e-09);
-    p = fma(p, r, 2.505210838544172e-08);
-    p = fma(p, r, 2.755731922398589e-07);
-    p = fma(p, r, 2.7557319223985893e-06);
-    p = fma(p, r, 2.48015873015873e-05);
-    p = fma(p, r, 1.984126984126984e-04);
-    p = fma(p, r, 1.388888888888889e-03);
-    p = fma(p, r, 8.333333333333333e-03);
-    p = fma(p, r, 4.1666666666666664e-02);
-    p = fma(p, r, 1.6666666666666666e-01);
+    p = mp_fma_c(p, r, 2.08767569878681e-09);
+    p = mp_fma_c(p, r, 2.505210838544172e-08);
+    p = mp_fma_c(p, r, 2.755731922398589e-07);
+    p = mp_fma_c(p, r, 2.7557319223985893e-06);
+    p = mp_fma_c(p, r, 2.48015873015873e-05);
+    p = mp_fma_c(p, r, 1.984126984126984e-04);
+    p = mp_fma_c(p, r, 1.388888888888889e-03);
+    p = mp_fma_c(p, r, 8.333333333333333e-03);
+    p = mp_fma_c(p, r, 4.1666666666666664e-02);
+    p = mp_fma_c(p, r, 1.6666666666666666e-01);
     p = fma(p, r, 0.5);
     const double y = 1.0 + fma(r * r, p, r);
     const int k = (int)kf;   // <= 0
@@ -463,7 +528,7 @@ __device__ __forceinline__ void normalize_tile(const double (&lw)[TILE / THREADS
     double m = MP_NEG_INF;
 #pragma unroll
     for (int j = 0; j < ITEMS_; ++j)
-        if (base + j < n) m = fmax(m, lw[j]);
+        if (base + j < n) m = mp_max_q(m, lw[j]);
     m = wave_max(m);
     MP_STAMP(0, 8, 0);
     if (lane == 0) s_red[wave] = m;
@@ -476,9 +541,7 @@ __device__ __forceinline__ void normalize_tile(const double (&lw)[TILE / THREADS
     else s_guide[tid] = 0;
     mp_lds_barrier();
     MP_STAMP(0, 9, 0);
-    m = s_red[0];
-#pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) m = fmax(m, s_red[w]);
+    m = xwave_max<THREADS / 64>(s_red, lane);
     const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
 
     u64 c[ITEMS_];
@@ -499,16 +562,8 @@ __device__ __forceinline__ void normalize_tile(const double (&lw)[TILE / THREADS
     if (lane == 0) s_wsum2[wave] = wtot2;
     mp_lds_barrier();
     MP_STAMP(0, 12, 0);
-    // cross-wave offsets on the scalar unit: the per-wave totals and `wave` are wave-uniform, so the sums need no VALU issue
-    u64 woff = 0, W = 0;
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-    for (int k = 0; k < THREADS / 64; ++k) {
-        const u64 vv = s_wsum[k];
-        const u64 v = ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(vv >> 32)) << 32) | (u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)vv);
-        if (k < wave_s) woff += v;
-        W += v;
-    }
+    u64 woff, W;
+    xwave_prefix<THREADS / 64>(s_wsum, lane, wave, woff, W);
     const u64 off = woff + (incl - run);
     MP_STAMP(0, 7, 0);
     // the tile's scalars go out (and the ticket is taken) now: its round trip is covered by the row stores and the guide
@@ -1030,7 +1085,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == 1024 ? 8 : (THREADS == 512 ? M
                 MP_STAMP(0, 29, 0);
                 double m = s_l1_red[0];
 #pragma unroll
-                for (int w = 1; w < THREADS / 64; ++w) m = fmax(m, s_l1_red[w]);
+                for (int w = 1; w < THREADS / 64; ++w) m = mp_max_q(m, s_l1_red[w]);
                 u64 incl = 0ull;
                 u64 T = 0ull;
                 if (wave_has) {
@@ -1088,7 +1143,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == 1024 ? 8 : (THREADS == 512 ? M
                 __syncthreads();
                 double m = s_l1_red[0];
 #pragma unroll
-                for (int w = 1; w < THREADS / 64; ++w) m = fmax(m, s_l1_red[w]);
+                for (int w = 1; w < THREADS / 64; ++w) m = mp_max_q(m, s_l1_red[w]);
                 const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
                 const double sc = mp_u2f((u64)(1023 + dw.S - FIX_BITS) << 52);  // 2^(S-51)
                 const u64 T0 = h0 ? mp_quantize((double)Wb0 * (ok ? mp_exp_nonpos(mb0 - m) : 0.) * sc, 1.0) : 0ull;
@@ -1233,7 +1288,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == 1024 ? 8 : (THREADS == 512 ? M
 #pragma unroll
                     for (int qq = 0; qq < G; ++qq) {   // (a lane reads only what it wrote: no barrier)
                         const double2 pr2 = s_pair[qq][threadIdx.x];
-                        zr[gr * G + qq] = mp_std_normal_from_pair(pr2.x, pr2.y);
+                        zr[gr * G + qq] = mp_std_normal_from_pair<(NS < 4)>(pr2.x, pr2.y);
                     }
                     continue;
                 }
@@ -1264,7 +1319,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == 1024 ? 8 : (THREADS == 512 ? M
                     }
                 }
 #pragma unroll
-                for (int qq = 0; qq < G; ++qq) zr[gr * G + qq] = mp_std_normal_from_pair(pu[qq], pr[qq]);
+                for (int qq = 0; qq < G; ++qq) zr[gr * G + qq] = mp_std_normal_from_pair<(NS < 4)>(pu[qq], pr[qq]);
             }
             if (cx_old) {
                 u64 ltr[ITEMS];
@@ -1352,7 +1407,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == 1024 ? 8 : (THREADS == 512 ? M
         }
         MP_STAMP(0, 22, 0);
 #pragma unroll
-        for (int q = 0; q < M; ++q) z[q] = mp_std_normal_from_pair(pu[q], pr[q]);
+        for (int q = 0; q < M; ++q) z[q] = mp_std_normal_from_pair<(NS < 4)>(pu[q], pr[q]);
     }
     MP_STAMP(0, 2, 0);
     if constexpr (!QUEUE) {
@@ -1571,7 +1626,7 @@ __device__ __forceinline__ double block_tile_table(const double* __restrict__ ti
     __syncthreads();
     m = s_red[0];
 #pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) m = fmax(m, s_red[w]);
+    for (int w = 1; w < THREADS / 64; ++w) m = mp_max_q(m, s_red[w]);
     const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
     const double sc = mp_u2f((u64)(1023 + S - FIX_BITS) << 52);  // 2^(S-51)
     u64 run = 0;
@@ -2088,7 +2143,7 @@ __global__ __launch_bounds__(1024) void k_peek_level1(const double* __restrict__
     __syncthreads();
     m = s_red[0];
 #pragma unroll
-    for (int w = 1; w < 16; ++w) m = fmax(m, s_red[w]);
+    for (int w = 1; w < 16; ++w) m = mp_max_q(m, s_red[w]);
     const bool ok = (m > MP_NEG_INF) && (m < MP_INF);
     const double sc = mp_u2f((u64)(1023 + S - FIX_BITS) << 52);  // 2^(S-51)
     u64 q = 0, q2 = 0;
