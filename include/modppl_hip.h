@@ -149,6 +149,19 @@ int32_t mp_pf_read_trajectory(mp_pf* h, uint64_t i, double* out, int32_t* t_step
 /* The same for the particles first .. first + count - 1 at once (one kernel walks the recorded ancestry of all of them):
  * out[count][t][dim_state].  tests/smc.rs:67 reads `retv` of every particle. */
 int32_t mp_pf_read_trajectories(mp_pf* h, uint64_t first, uint64_t count, double* out, int32_t* t_steps);
+/* Smoothed mean and variance of the state at EVERY time step, over the recorded ancestry, reduced ON THE DEVICE: replaces walking
+ * `traces[i].retv` of every particle (particle_filter.rs:13; tests/smc.rs:67) and reducing on the host, i.e. mp_pf_read_trajectories
+ * (n * T * dim_state doubles over the link) and a loop.  With T = mp_pf_time, v_i(t) = the state at time t of slot i's ancestor (the
+ * walk of mp_pf_read_trajectories) and the weights a_i of mp_pf_moments:
+ *   mean_out[t][j] = sum_i a_i v_ij(t) / sum_i a_i;   var_out[t][j] = sum_i a_i (v_ij(t) - mean_tj)^2 / sum_i a_i   (population form;
+ * marginal variances only; NULL = means only).  distinct_out[t] (or NULL) = the number of distinct ancestors at time t of the n slots,
+ * weights ignored: the path-degeneracy diagnostic, non-decreasing in t.  The caller sizes mean_out / var_out [T][dim_state] and
+ * distinct_out[T] from mp_pf_time; *t_steps = T.  Every sum is the pairwise tree over GLOBAL slot ids of DESIGN.md section 4, so row
+ * T - 1 equals mp_pf_moments' mean and the diagonal of its covariance bit for bit.  Synchronous, on the handle's stream; brings the
+ * handle to a readable state exactly as mp_pf_read_trajectories followed by mp_pf_read_log_weights do and changes nothing the filter
+ * computes afterwards.  Needs MP_PF_RECORD_HISTORY (else MP_ERR_STATE; also before init_step).  All log-weights -inf:
+ * MP_ERR_DEGENERATE.  One shard of a larger world, or a dim_state other than 1, 2, 4, 16: MP_ERR_UNSUPPORTED. */
+int32_t mp_pf_path_moments(mp_pf* h, double* mean_out, double* var_out, uint64_t* distinct_out, int32_t* t_steps);
 /* Number of Unfold steps taken so far (trace.args.0). */
 int32_t mp_pf_time(mp_pf* h, int64_t* out);
 /* Whole filter in one call: init_step on obs[0], then for t=1..T-1 {step; resample} with a

@@ -95,6 +95,19 @@ public:
         check(mp_pf_moments(h_, m.mean.data(), cov ? m.cov.data() : nullptr));
         return m;
     }
+    // smoothed mean and population variance of the state at every time step, [t][dim_state] row-major, and the number of distinct
+    // ancestors per step, reduced on the device over the recorded ancestry (mp_pf_path_moments; a filter created with
+    // MP_PF_RECORD_HISTORY): walking traces[i].retv of every particle and reducing on the host, without moving n * t * dim_state doubles
+    struct PathMoments { std::vector<double> mean, var; std::vector<uint64_t> distinct; };
+    PathMoments path_moments(bool var = true, bool distinct = false) {
+        int64_t t = 0;
+        check(mp_pf_time(h_, &t));
+        const size_t T = (size_t)t, td = T * (size_t)model_.dim_state;
+        PathMoments m{std::vector<double>(td), std::vector<double>(var ? td : 0), std::vector<uint64_t>(distinct ? T : 0)};
+        int32_t steps = 0;
+        check(mp_pf_path_moments(h_, m.mean.data(), var ? m.var.data() : nullptr, distinct ? m.distinct.data() : nullptr, &steps));
+        return m;
+    }
     std::vector<double> log_weights() {
         std::vector<double> w(n_);
         check(mp_pf_read_log_weights(h_, w.data()));

@@ -20,6 +20,10 @@
 //   count_s = TREE(p_i) (a sum of 0.0 / 1.0: exact);  mean_s = TREE(p_i ? v_i : +0.0) / count_s;
 //   var_s = TREE(p_i ? (v_i - mean_s)^2 : +0.0) / count_s      (selected, never multiplied: a stale NaN in an absent slot cannot leak)
 //
+// Path moments (mp_pf_path_moments; DESIGN.md §4, "Path moments"): the same weights and trees over v_i(t) = x_t[anc_i(t)], the state of
+//   slot i's ancestor at time t along the recorded history, for every t: mean_tj = TREE(a_i v_ij(t)) / A;
+//   var_tj = TREE(a_i (v_ij(t) - mean_tj)^2) / A;  distinct_t = |{anc_i(t)}| (a bitmap and a popcount: integers).
+//
 // Registers (gfx950 code object, kernel-resource-usage): k_mom_pf2<16> holds c[R = 4][16] and a[4] per lane and walks the 136 (j, k)
 // pairs one at a time — one accumulator tree per pair, never 136 live accumulators; see DESIGN.md §5 for the VGPR / scratch figures.
 #pragma once
@@ -175,6 +179,144 @@ __global__ __launch_bounds__(MOM_THREADS) void k_mom_pf2(unsigned long long n, c
     __syncthreads();
     const int ncols = d * (d + 1) / 2;
     if ((int)threadIdx.x < ncols) out[(unsigned long long)threadIdx.x * gridDim.x + blockIdx.x] = mom_block_combine<mom_add>((int)threadIdx.x, s_part);
+}
+
+// ---- path moments (mp_pf_path_moments): the same trees over v_i(t) = x_t[anc_i(t)], gathered along the recorded ancestry ------------------
+// A lane owns the aligned run of R slots k_mom_pf1 gives it (so the tree is cut where that kernel cuts it), keeps their weights and
+// their current ancestor slots in registers and walks the event log (mp_hist_event, mp_pf_kernels.h) from the newest event back, as
+// k_trajectories does: a resample maps anc <- parents[anc], a step is time t read at anc.  The log is uniform, so its entries are
+// scalar loads and every branch on them is taken by the whole grid.  One partial per (t, j, workgroup): out[(t d + j) nb + b]; the
+// LDS partials alternate between two buffers, so a step event costs one __syncthreads (a wave that runs ahead writes the buffer
+// nobody reads before the next barrier).  Slots past n gather row 0 (in bounds) and are selected to +0.0, never multiplied.
+template <int DP>
+__device__ __forceinline__ void mom_load_row(const double* __restrict__ p, double (&v)[DP]) {
+    if constexpr (DP == 1) {
+        v[0] = p[0];
+    } else {   // rows of an even width start on 16 bytes (the history buffers are 256-byte aligned): dwordx4 loads
+        const double2* q = reinterpret_cast<const double2*>(p);
+#pragma unroll
+        for (int j = 0; j < DP / 2; ++j) { const double2 w = q[j]; v[2 * j] = w.x; v[2 * j + 1] = w.y; }
+    }
+}
+
+// pass 1: out[(t d + j) nb + b] = subtree of a_i v_ij(t), out[T d nb + b] = subtree of a_i.  bitmap (or null): bit anc_i(t) of row t
+// of [T][words] u32 is set for every slot i < n — integer ORs, exact in any order (k_path_distinct counts them).
+template <int DP>
+__global__ __launch_bounds__(MOM_THREADS) void k_path_mom1(unsigned long long n, int n_events, int T, const mp_hist_event* __restrict__ ev,
+                                                           const double* __restrict__ lw, const double* __restrict__ m_ptr, double* __restrict__ out,
+                                                           uint32_t* __restrict__ bitmap, unsigned long long words) {
+    constexpr int R = mom_run<DP>::R;
+    __shared__ double s_part[2][DP * MOM_WAVES];
+    __shared__ double s_a[MOM_WAVES];
+    const double m = *m_ptr;
+    const unsigned long long nb = gridDim.x;
+    const unsigned long long i0 = ((unsigned long long)blockIdx.x * MOM_THREADS + threadIdx.x) * R;
+    double a[R], t[R];
+    uint32_t anc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        a[r] = (i0 + r < n) ? mom_weight(lw[i0 + r], m) : 0.;
+        anc[r] = (i0 + r < n) ? (uint32_t)(i0 + r) : 0u;
+        t[r] = a[r];
+    }
+    mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(t), 0, s_a);
+    __syncthreads();
+    if (threadIdx.x == 0) out[(unsigned long long)T * DP * nb + blockIdx.x] = mom_block_combine<mom_add>(0, s_a);
+    int tt = T, pb = 0;
+    for (int e = n_events - 1; e >= 0; --e) {
+        const void* buf = ev[e].buf;
+        if (ev[e].kind == 1) {
+            const uint32_t* parents = static_cast<const uint32_t*>(buf);
+#pragma unroll
+            for (int r = 0; r < R; ++r) anc[r] = parents[anc[r]];
+            continue;
+        }
+        --tt;
+        const double* x = static_cast<const double*>(buf);
+        double v[R][DP];
+#pragma unroll
+        for (int r = 0; r < R; ++r) mom_load_row<DP>(x + (unsigned long long)anc[r] * DP, v[r]);
+        if (bitmap) {
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (i0 + r < n) atomicOr(&bitmap[(unsigned long long)tt * words + (anc[r] >> 5)], 1u << (anc[r] & 31u));
+        }
+        double* sp = s_part[pb];
+#pragma unroll
+        for (int j = 0; j < DP; ++j) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) t[r] = (i0 + r < n) ? a[r] * v[r][j] : 0.;
+            mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(t), j, sp);
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < DP) out[((unsigned long long)tt * DP + threadIdx.x) * nb + blockIdx.x] = mom_block_combine<mom_add>((int)threadIdx.x, sp);
+        pb ^= 1;
+    }
+}
+
+// pass 2: out[(t d + j) nb + b] = subtree of a_i (v_ij(t) - mean_tj)^2.  sums = the closed trees of pass 1 ({S[T][d], A}); every lane
+// forms mean_tj = S_tj / A itself (same bits), workgroup 0 stores it.  One component at a time: the gathered rows stay live (R DP
+// doubles), the centred values never do.
+template <int DP>
+__global__ __launch_bounds__(MOM_THREADS) void k_path_mom2(unsigned long long n, int n_events, int T, const mp_hist_event* __restrict__ ev,
+                                                           const double* __restrict__ lw, const double* __restrict__ m_ptr, const double* __restrict__ sums,
+                                                           double* __restrict__ mean_out, double* __restrict__ out) {
+    constexpr int R = mom_run<DP>::R;
+    __shared__ double s_part[2][DP * MOM_WAVES];
+    const double m = *m_ptr;
+    const double A = sums[(unsigned long long)T * DP];
+    const unsigned long long nb = gridDim.x;
+    const unsigned long long i0 = ((unsigned long long)blockIdx.x * MOM_THREADS + threadIdx.x) * R;
+    double a[R], t[R];
+    uint32_t anc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        a[r] = (i0 + r < n) ? mom_weight(lw[i0 + r], m) : 0.;
+        anc[r] = (i0 + r < n) ? (uint32_t)(i0 + r) : 0u;
+    }
+    int tt = T, pb = 0;
+    for (int e = n_events - 1; e >= 0; --e) {
+        const void* buf = ev[e].buf;
+        if (ev[e].kind == 1) {
+            const uint32_t* parents = static_cast<const uint32_t*>(buf);
+#pragma unroll
+            for (int r = 0; r < R; ++r) anc[r] = parents[anc[r]];
+            continue;
+        }
+        --tt;
+        const double* x = static_cast<const double*>(buf);
+        double v[R][DP];
+#pragma unroll
+        for (int r = 0; r < R; ++r) mom_load_row<DP>(x + (unsigned long long)anc[r] * DP, v[r]);
+        double* sp = s_part[pb];
+#pragma unroll
+        for (int j = 0; j < DP; ++j) {
+            const double mean = sums[(unsigned long long)tt * DP + j] / A;
+            if (blockIdx.x == 0 && threadIdx.x == 0) mean_out[(unsigned long long)tt * DP + j] = mean;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double c = (i0 + r < n) ? v[r][j] - mean : 0.;
+                t[r] = (i0 + r < n) ? a[r] * (c * c) : 0.;
+            }
+            mom_block_put<mom_add>(mom_lane_tree<mom_add, R>(t), j, sp);
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < DP) out[((unsigned long long)tt * DP + threadIdx.x) * nb + blockIdx.x] = mom_block_combine<mom_add>((int)threadIdx.x, sp);
+        pb ^= 1;
+    }
+}
+
+// distinct[t] = the set bits of row t of the bitmap: one workgroup per t, integer adds (exact in any order)
+__global__ __launch_bounds__(MOM_THREADS) void k_path_distinct(const uint32_t* __restrict__ bitmap, unsigned long long words, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s_cnt[MOM_WAVES];
+    const uint32_t* row = bitmap + (unsigned long long)blockIdx.x * words;
+    unsigned long long cnt = 0;
+    for (unsigned long long w = threadIdx.x; w < words; w += MOM_THREADS) cnt += (unsigned long long)__popc(row[w]);
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) cnt += __shfl_xor(cnt, s, 64);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
 }
 
 #endif   // MP_MOMENTS_PF

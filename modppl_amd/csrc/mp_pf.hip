@@ -422,6 +422,12 @@ struct mp_pf {
     mp_dev<double> mom_buf[2];
     mp_dev<double> mom_res;                // {m, A, S[d], mean[d], C[d (d + 1) / 2]}
     mp_pinned<double> mom_host;            // ... and where they land on the host
+    // mp_pf_path_moments, sized on first use and grown with the time: the same three, for T * d columns (+ A), and the ancestor bitmap
+    mp_dev<double> path_buf[2];
+    mp_dev<double> path_res;               // {m, S[T][d], A, mean[T][d], V[T][d], distinct u64[T]}
+    mp_pinned<double> path_host;
+    mp_dev<uint32_t> path_bits;            // [T][ceil(n / 32)]
+    size_t path_cap_t = 0, path_bits_cap_t = 0;   // the T they hold
     // host-side filter state
     long long t = 0;  // Unfold steps taken (trace.args.0)
     uint32_t resample_count = 0;
@@ -793,6 +799,41 @@ static void launch_moments_pass(mp_pf* h, int pass, unsigned nb, const double* x
     else
         hipLaunchKernelGGL((k_mom_pf2<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, x, (const double*)h->logw, (const double*)res,
                            (const double*)(res + 1), res + 2 + D, h->mom_buf[0].get());
+}
+
+// the event log as the history kernels read it (k_trajectories, k_path_mom1/2), enqueued on the handle's stream; `ev` is the caller's
+// and stays alive until it has waited for the stream
+static int32_t upload_hist_events(mp_pf* h, std::vector<mp_hist_event>& ev) {
+    ev.resize(h->hist.size());
+    for (size_t e = 0; e < h->hist.size(); ++e) { ev[e].buf = h->hist[e].buf; ev[e].kind = h->hist[e].kind; ev[e].pad = 0; }
+    if (h->d_hist_events_cap < ev.size()) {
+        h->d_hist_events_cap = 0;
+        const size_t cap = std::max<size_t>(64, 2 * ev.size());
+        HIPCK(mp_hipMalloc(h->d_hist_events, cap));
+        h->d_hist_events_cap = cap;
+    }
+    HIPCK(hipMemcpyAsync(h->d_hist_events, ev.data(), sizeof(mp_hist_event) * ev.size(), hipMemcpyHostToDevice, h->stream));
+    return MP_OK;
+}
+
+// mp_pf_path_moments: the level-0 walk of pass 1 or 2 for a state width D; res = {m, S[T][D], A, mean[T][D], ...}
+template <int D>
+static void launch_path_pass(mp_pf* h, int pass, unsigned nb, int T, double* res, uint32_t* bitmap, u64 words) {
+    const mp_hist_event* ev = h->d_hist_events;
+    if (pass == 1)
+        hipLaunchKernelGGL((k_path_mom1<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, (int)h->hist.size(), T, ev, (const double*)h->logw,
+                           (const double*)res, h->path_buf[0].get(), bitmap, words);
+    else
+        hipLaunchKernelGGL((k_path_mom2<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, (int)h->hist.size(), T, ev, (const double*)h->logw,
+                           (const double*)res, (const double*)(res + 1), res + 2 + (size_t)T * D, h->path_buf[0].get());
+}
+// mom_close for more columns than a grid has rows: slices of at most 65535 columns, each closing inside its own part of the two buffers
+static void path_close(hipStream_t stream, double* const buf[2], u64 nb, u64 cols, double* dst) {
+    const u64 nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
+    for (u64 c0 = 0; c0 < cols; c0 += 65535) {
+        double* const part[2] = {buf[0] + c0 * nb, buf[1] + c0 * nn};
+        mom_close<mom_add>(stream, part, nb, (unsigned)std::min<u64>(65535, cols - c0), dst + c0);
+    }
 }
 
 extern "C" {
@@ -1883,16 +1924,8 @@ int32_t mp_pf_read_trajectories(mp_pf* h, uint64_t first, uint64_t count, double
     const int T = (int)h->t;
     *t_steps = (int32_t)h->t;
     if (T == 0) return MP_OK;
-    // the event log as the kernel reads it
-    std::vector<mp_hist_event> ev(h->hist.size());
-    for (size_t e = 0; e < h->hist.size(); ++e) { ev[e].buf = h->hist[e].buf; ev[e].kind = h->hist[e].kind; ev[e].pad = 0; }
-    if (h->d_hist_events_cap < ev.size()) {
-        h->d_hist_events_cap = 0;
-        const size_t cap = std::max<size_t>(64, 2 * ev.size());
-        HIPCK(mp_hipMalloc(h->d_hist_events, cap));
-        h->d_hist_events_cap = cap;
-    }
-    HIPCK(hipMemcpyAsync(h->d_hist_events, ev.data(), sizeof(mp_hist_event) * ev.size(), hipMemcpyHostToDevice, h->stream));
+    std::vector<mp_hist_event> ev;
+    MPCK(upload_hist_events(h, ev));
     mp_dev<double> d_out;
     const size_t bytes = sizeof(double) * (size_t)count * (size_t)T * (size_t)d;
     HIPCK(mp_hipMalloc(d_out, (size_t)count * (size_t)T * (size_t)d));
@@ -1907,6 +1940,83 @@ int32_t mp_pf_read_trajectories(mp_pf* h, uint64_t first, uint64_t count, double
 
 int32_t mp_pf_read_trajectory(mp_pf* h, uint64_t i, double* out, int32_t* t_steps) {
     return mp_pf_read_trajectories(h, i, 1, out, t_steps);
+}
+
+// Smoothed mean and variance per time step over the recorded ancestry, and the number of distinct ancestors per step, reduced on the
+// device: replaces walking `traces[i].retv` of every particle (particle_filter.rs:13; tests/smc.rs:67) — here mp_pf_read_trajectories,
+// n * T * d doubles over the link — and a host loop.  Definition: mp_moments.h, DESIGN.md section 4, "Path moments".
+// As in mp_pf_moments every launch is enqueued before the one wait.
+int32_t mp_pf_path_moments(mp_pf* h, double* mean_out, double* var_out, uint64_t* distinct_out, int32_t* t_steps) {
+    if (!h || !mean_out || !t_steps) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
+    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_path_moments: ancestors of a sharded filter live on other ranks");
+    if (!(h->flags & MP_PF_RECORD_HISTORY)) return mp_fail(MP_ERR_STATE, "path_moments needs a filter created with MP_PF_RECORD_HISTORY");
+    if (!h->initialised) return mp_fail(MP_ERR_STATE, "path_moments before init_step");
+    const int d = h->ops->dim_state;
+    if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_path_moments: no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
+    HIPCK(hipSetDevice(h->device));
+    MPCK(materialize(h));
+    MPCK(ensure_x(h));
+    MPCK(ensure_lazy(h));
+    const int T = (int)h->t;
+    *t_steps = (int32_t)h->t;
+    if (T == 0) return MP_OK;
+    size_t n_step_events = 0;
+    for (const auto& e : h->hist) n_step_events += e.kind == 0;
+    if (n_step_events != (size_t)T) return mp_fail(MP_ERR_STATE, "mp_pf_path_moments: the recorded history does not hold one state per step");
+    const int R = d <= 4 ? 8 : 4;   // mom_run<D>::R
+    const u64 nb = (h->n + (u64)MOM_THREADS * R - 1) / ((u64)MOM_THREADS * R);
+    const u64 nb_max = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);   // (<= nb)
+    const u64 nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
+    const size_t TD = (size_t)T * d;
+    const size_t n_res = 2 + 3 * TD + (size_t)T;
+    if (h->path_cap_t < (size_t)T) {
+        const size_t cap = std::max<size_t>(16, 2 * (size_t)T), cols = cap * d + 1;
+        h->path_cap_t = 0;
+        HIPCK(mp_hipMalloc(h->path_buf[0], cols * nb));
+        HIPCK(mp_hipMalloc(h->path_buf[1], cols * nn));
+        HIPCK(mp_hipHostMalloc(h->path_host, 2 + 3 * cap * d + cap));
+        HIPCK(mp_hipMalloc(h->path_res, 2 + 3 * cap * d + cap));
+        h->path_cap_t = cap;
+    }
+    const u64 words = (h->n + 31) / 32;
+    if (distinct_out && h->path_bits_cap_t < (size_t)T) {
+        const size_t cap = std::max<size_t>(16, 2 * (size_t)T);
+        h->path_bits_cap_t = 0;
+        HIPCK(mp_hipMalloc(h->path_bits, cap * words));
+        h->path_bits_cap_t = cap;
+    }
+    std::vector<mp_hist_event> ev;
+    MPCK(upload_hist_events(h, ev));
+    double* const buf[2] = {h->path_buf[0].get(), h->path_buf[1].get()};
+    double* res = h->path_res;
+    unsigned long long* d_distinct = reinterpret_cast<unsigned long long*>(res + 2 + 3 * TD);
+    uint32_t* bitmap = distinct_out ? h->path_bits.get() : nullptr;
+    if (bitmap) HIPCK(hipMemsetAsync(bitmap, 0, sizeof(uint32_t) * (size_t)T * words, h->stream));
+    hipLaunchKernelGGL(k_mom_max0, dim3((unsigned)nb_max), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->logw, buf[0]);
+    mom_close<mom_max>(h->stream, buf, nb_max, 1, res);
+    for (int pass = 1; pass <= (var_out ? 2 : 1); ++pass) {
+        switch (d) {
+        case 1: launch_path_pass<1>(h, pass, (unsigned)nb, T, res, bitmap, words); break;
+        case 2: launch_path_pass<2>(h, pass, (unsigned)nb, T, res, bitmap, words); break;
+        case 4: launch_path_pass<4>(h, pass, (unsigned)nb, T, res, bitmap, words); break;
+        default: launch_path_pass<16>(h, pass, (unsigned)nb, T, res, bitmap, words); break;
+        }
+        path_close(h->stream, buf, nb, pass == 1 ? TD + 1 : TD, pass == 1 ? res + 1 : res + 2 + 2 * TD);
+    }
+    if (bitmap) hipLaunchKernelGGL(k_path_distinct, dim3((unsigned)T), dim3(MOM_THREADS), 0, h->stream, (const uint32_t*)bitmap, words, d_distinct);
+    hipError_t e1 = hipGetLastError();
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(h->path_host, res, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream);
+    if (e1 != hipSuccess) { (void)hipStreamSynchronize(h->stream); return mp_fail(MP_ERR_HIP, std::string("mp_pf_path_moments: ") + hipGetErrorString(e1)); }   // (ev stays alive until the stream is idle)
+    MPCK(stream_wait(h->stream));
+    const double* r = h->path_host;
+    if (r[0] == -MP_INF) return mp_fail_degenerate();
+    const double A = r[1 + TD];
+    // without a variance pass nobody has formed the means on the device: the same IEEE division here
+    for (size_t c = 0; c < TD; ++c) mean_out[c] = var_out ? r[2 + TD + c] : r[1 + c] / A;
+    if (var_out)
+        for (size_t c = 0; c < TD; ++c) var_out[c] = r[2 + 2 * TD + c] / A;
+    if (distinct_out) memcpy(distinct_out, r + 2 + 3 * TD, sizeof(uint64_t) * (size_t)T);
+    return MP_OK;
 }
 
 int32_t mp_pf_time(mp_pf* h, int64_t* out) {

@@ -184,6 +184,21 @@ class ParticleSystem:
         capi.check(self._L.mp_pf_read_trajectories(self._h, int(first), count, _dptr(out), C.byref(t)))
         return out[:, : t.value]
 
+    def path_moments(self, var=True, distinct=False):
+        """-> (mean [t, dim_state], var [t, dim_state] or None, distinct uint64 [t] or None): the smoothed mean and (population,
+        marginal) variance of the state at every time step — the weighted moments of `trajectories()` under the current log-weights —
+        and the number of distinct ancestors the particles have at each step, reduced on the device by one walk of the recorded
+        ancestry per pass (mp_pf_path_moments; needs flags=MP_PF_RECORD_HISTORY).  Same trees as `moments()`:
+        mean[-1] and var[-1] are its mean and diag(cov), bit for bit."""
+        T, d = max(self.time, 1), self.model.dim_state
+        mean = np.empty((T, d))
+        v = np.empty((T, d)) if var else None
+        k = np.empty(T, dtype=np.uint64) if distinct else None
+        t = C.c_int32()
+        capi.check(self._L.mp_pf_path_moments(self._h, _dptr(mean), _dptr(v) if var else None,
+                                              k.ctypes.data_as(C.POINTER(C.c_uint64)) if distinct else None, C.byref(t)))
+        return mean[: t.value], (v[: t.value] if var else None), (k[: t.value] if distinct else None)
+
     def set_timing(self, enabled):
         capi.check(self._L.mp_pf_set_timing(self._h, int(enabled)))
 

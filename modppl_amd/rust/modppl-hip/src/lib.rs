@@ -91,6 +91,18 @@ impl ParticleSystem {
         check(unsafe { sys::mp_pf_moments(self.h, mean.as_mut_ptr(), cov.as_mut_ptr()) });
         (mean, cov)
     }
+    /// Smoothed mean and population variance of the state at every time step (`[t][dim_state]`, row-major) and the number of distinct
+    /// ancestors per step, reduced on the device over the recorded ancestry (a filter created with `MP_PF_RECORD_HISTORY`): what
+    /// walking `traces[i].retv` of every particle and a host loop give, without moving `n * t * dim_state` doubles.
+    pub fn path_moments(&self) -> (Vec<f64>, Vec<f64>, Vec<u64>) {
+        let mut t = 0i64;
+        check(unsafe { sys::mp_pf_time(self.h, &mut t) });
+        let (t, d) = (t as usize, self.model.dim_state as usize);
+        let (mut mean, mut var, mut distinct) = (vec![0.0; t * d], vec![0.0; t * d], vec![0u64; t]);
+        let mut steps = 0i32;
+        check(unsafe { sys::mp_pf_path_moments(self.h, mean.as_mut_ptr(), var.as_mut_ptr(), distinct.as_mut_ptr(), &mut steps) });
+        (mean, var, distinct)
+    }
     /// `log_weights` (pub field of the reference's struct)
     pub fn log_weights(&self) -> Vec<f64> {
         let mut w = vec![0.0; self.num_particles];
