@@ -184,8 +184,10 @@ struct ModelOpsT : ModelOps {
         }
         if constexpr (THREADS == 1024 && Model::DIM_STATE == 1 && 2 * Model::MAX_NORMALS <= 4) {
             // one workgroup per CU walking several tiles (mp_pf_k1mt.h): drawing launches of unsharded filters with at most one table
-            // entry per thread
-            if (a.drw == 1 && a.mt_grid > 0 && a.drw_v.nt <= 1024 && a.drw_v.nt >= 2 * a.mt_grid && a.cx_old && !a.inv && !a.inv_rows) {
+            // entry per thread.  (nt <= MP_MT_MAX_TILES is also what lets the kernel keep every row index and byte offset in 32 bits:
+            // the static_assert in mp_pf_k1mt.h)
+            static_assert(MP_MT_MAX_TILES == THREADS, "k_propagate_mt: one table entry per thread");
+            if (a.drw == 1 && a.mt_grid > 0 && a.drw_v.nt <= MP_MT_MAX_TILES && a.drw_v.nt >= 2 * a.mt_grid && a.cx_old && !a.inv && !a.inv_rows) {
                 // (multinomial draws, jobs of at least two tiles per CU: below that one workgroup per tile spreads over more CUs —
                 // 2^17 particles 23 against 32 us —, and a lattice's sorted lookups leave nothing to hide: 30.0 against 31.5 us;
                 // 2^20: 38.6 against 38.9, 2^21: 80.9 against 85.9, profiles/r04/k1_scaling.txt)

@@ -53,9 +53,20 @@ constexpr int MP_MT_SKIP_LOGW = 1, MP_MT_SKIP_PARENT = 2;
 constexpr int MP_MT_REPLAY = 4;
 constexpr int MP_MT_PEEK = 8;
 
+// Rows and addresses in 32 bits.  The kernel is launched only for jobs of at most MP_MT_MAX_TILES tiles (`a.drw_v.nt <= MP_MT_MAX_TILES`,
+// ModelOpsT::propagate in mp_pf.hip: one table entry per thread), i.e. at most 2^21 rows, so a row index, a slot of the handle, a
+// tile base and the BYTE offset of a row in the widest per-row array (16-byte mp_cx rows: below 2^25) all fit a uint32_t.  Inside
+// the kernel n, every row index and every offset is a uint32_t, and every access whose base is a launch constant is that base (an
+// SGPR pair) plus a 32-bit byte offset (mp_at32 / mp_ld_row32, mp_pf_kernels.h) — no 64-bit vector adds, compares, selects or
+// shift-adds to form them.  Cumulative weights, targets and fixed-point sums ARE 64-bit quantities and stay so; the Philox counter
+// of a slot is the low word of slot_offset + slot either way ((uint32_t)(x + y) == (uint32_t)x + (uint32_t)y), while the
+// resample block's counter (slot_offset + slot) >> 1 needs the carry out of bit 31 and is still formed in 64 bits.
+constexpr int MP_MT_MAX_TILES = 1024;
+static_assert((unsigned long long)MP_MT_MAX_TILES * TILE * sizeof(mp_cx) < (1ull << 32), "k_propagate_mt: byte offsets of table rows in 32 bits");
+
 // what a lane carries for one of its tiles between the stages of the pipeline
 struct mp_mt_tile {
-    u64 base;               // first of the lane's two slots (local to the handle)
+    uint32_t base;          // first of the lane's two slots (local to the handle)
     u64 plt[2];             // tile-local targets of its two draws
     uint32_t tile_of[2];    // the draws' tiles, then (mt_rows) their start rows
     uint32_t g[2];          // guide cells (in flight after mt_draw)
@@ -65,9 +76,9 @@ struct mp_mt_tile {
 
 // stage 1: the two draws of the lane's slots of tile `tile`: targets, tile walk in the LDS table, guide cells requested
 template <bool WALKB>
-__device__ __forceinline__ void mt_draw(mp_mt_tile& T, u64 tile, const mp_u64x2& blk, const mp_k1mt& a, int nt,
+__device__ __forceinline__ void mt_draw(mp_mt_tile& T, uint32_t tile, const mp_u64x2& blk, const mp_k1mt& a, int nt,
                                         const u64* s_incl, const u64* s_W, const double* s_ratio, u64 Q, double nt_over_Q) {
-    T.base = tile * TILE + (u64)threadIdx.x * 2;
+    T.base = tile * (uint32_t)TILE + threadIdx.x * 2u;
 #if MP_MT_PROBE & 8
     for (int q = 0; q < 2; ++q) {
         T.tile_of[q] = (uint32_t)tile;
@@ -84,7 +95,7 @@ __device__ __forceinline__ void mt_draw(mp_mt_tile& T, u64 tile, const mp_u64x2&
         mp_locate_r<WALKB>(s_incl, s_W, s_ratio, (uint32_t)nt, tg, nt_over_Q, &T.tile_of[q], &T.plt[q], &gslot[q], &T.sp[q]);
     }
 #pragma unroll
-    for (int q = 0; q < 2; ++q) T.g[q] = a.guide_old[gslot[q]];
+    for (int q = 0; q < 2; ++q) T.g[q] = *mp_at32(a.guide_old, gslot[q] * (uint32_t)sizeof(unsigned short));
 }
 // stage 2: start rows from the guide cells; the rows requested.  MP_MT_Q5 (default): the cell's position bits against the target's own
 // 32nd of the cell (mp_guide_q5 / mp_guide_sub, mp_pf_kernels.h) say which rows — r0 ALONE when the target lies below cum[r0] (39 % of
@@ -108,15 +119,15 @@ __device__ __forceinline__ double mt_probe_deviate(u64 slot, long long t, int sa
     h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
     return (double)(h & 0xFFFFFu) * (3.4641016 / 1048576.) - 1.7320508;   // uniform, variance 1
 }
-__device__ __forceinline__ void mt_rows(mp_mt_tile& T, const mp_k1mt& a) {
+__device__ __forceinline__ void mt_rows(mp_mt_tile& T, const mp_k1mt& a, uint32_t n) {
     bool hbv[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const u64 tbase = (u64)T.tile_of[q] * TILE;
-        const uint32_t tlen = (uint32_t)((a.n - tbase) < (u64)TILE ? (a.n - tbase) : (u64)TILE);
+        const uint32_t tbase = T.tile_of[q] * (uint32_t)TILE;
+        const uint32_t tlen = n - tbase < (uint32_t)TILE ? n - tbase : (uint32_t)TILE;
         const uint32_t j0 = mp_guide_row(T.g[q]);
-        uint32_t r0 = (uint32_t)tbase + (j0 > tlen - 1 ? tlen - 1 : j0);   // row where the forward scan starts
-        const uint32_t last = (uint32_t)tbase + tlen - 1;
+        uint32_t r0 = tbase + (j0 > tlen - 1 ? tlen - 1 : j0);   // row where the forward scan starts
+        const uint32_t last = tbase + tlen - 1;
         if constexpr (MP_MT_Q5 != 0) {
             const uint32_t q5 = mp_guide_q5(T.g[q]);
             const bool below = T.sp[q] < q5, above = T.sp[q] > q5;
@@ -140,10 +151,17 @@ __device__ __forceinline__ void mt_rows(mp_mt_tile& T, const mp_k1mt& a) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const uint32_t r0 = T.tile_of[q];
-        T.a[q] = mp_ld_row(a.cx_old + r0);
+        T.a[q] = mp_ld_row32(a.cx_old, r0);
         // (a lane that wants no second row reads row 0 of the table with every other such lane of the chip — or, without the position bits,
         // its own row again, as before)
-        T.b2[q] = mp_ld_row(a.cx_old + (hbv[q] ? (u64)r0 + 1 : (MP_MT_Q5 != 0 ? 0ull : (u64)r0)));
+        // (`hbv ? r0 + 1 : 0` as a 32-bit minimum under a limit of ~0 or 0: the select against the constant 0 becomes a 64-bit select between
+        // two ADDRESSES, and mp_keep32 on it, here, costs more SGPR spills than the address saves)
+        if constexpr (MP_MT_Q5 != 0) {
+            const uint32_t lim = hbv[q] ? ~0u : 0u;
+            T.b2[q] = mp_ld_row32(a.cx_old, r0 + 1u < lim ? r0 + 1u : lim);
+        } else {
+            T.b2[q] = mp_ld_row32(a.cx_old, r0 + (hbv[q] ? 1u : 0u));
+        }
         T.sp[q] = hbv[q] ? 1u : 0u;                                  // (from here on: whether b2 is the successor)
     }
 }
@@ -161,18 +179,18 @@ struct mp_mt_walk {
     mp_u64v2 nx[2][MP_MT_WALK_ROWS];     // (more) the rows p + 1 ..: requested, not yet looked at
     bool more[2];
 };
-__device__ __forceinline__ void mt_resolve_first(mp_mt_tile& T, const mp_k1mt& a, mp_mt_walk& W) {
+__device__ __forceinline__ void mt_resolve_first(mp_mt_tile& T, const mp_k1mt& a, uint32_t n, mp_mt_walk& W) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) mp_pin_rows(T.a[q], T.b2[q]);   // the rows are looked at here, not earlier
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const uint32_t r0 = T.tile_of[q];
-        const u64 last = mp_tile_last(r0, a.n);
+        const uint32_t last = mp_tile_last32(r0, n);
         const bool hb = T.sp[q] != 0u;                          // (mt_rows: the successor was asked for)
         const bool step1 = T.a[q].x < T.plt[q] && hb;
         W.p[q] = r0 + (step1 ? 1u : 0u);
         W.cur[q] = step1 ? T.b2[q] : T.a[q];
-        W.more[q] = W.cur[q].x < T.plt[q] && (u64)W.p[q] < last;
+        W.more[q] = W.cur[q].x < T.plt[q] && W.p[q] < last;
         // more than one row past the guide's start (a successor in the next 64-byte line, mostly): the next rows, asked for by EVERY
         // lane — the lanes that need none read row 0, one line for the whole wave — so that this is straight-line code: behind a
         // branch the compiler no longer knows how many loads are in flight and waits for all of them, the next tile's included
@@ -181,18 +199,19 @@ __device__ __forceinline__ void mt_resolve_first(mp_mt_tile& T, const mp_k1mt& a
 #if MP_MT_PROBE & 2
             W.nx[q][k] = W.cur[q];
 #else
-            const u64 r = (u64)W.p[q] + 1 + k;
-            W.nx[q][k] = mp_ld_row(a.cx_old + (W.more[q] ? (r < last ? r : last) : 0ull));
+            const uint32_t r = W.p[q] + 1u + (uint32_t)k;
+            // (mp_keep32: the select against row 0 stays a select between two 32-bit offsets, not between two addresses)
+            W.nx[q][k] = mp_ld_row32(a.cx_old, mp_keep32(W.more[q] ? (r < last ? r : last) : 0u));
 #endif
         }
     }
 }
 template <bool WALKB>
-__device__ __forceinline__ void mt_resolve_rest(const mp_mt_tile& T, const mp_k1mt& a, mp_mt_walk& W, uint32_t* parent, double* x0) {
+__device__ __forceinline__ void mt_resolve_rest(const mp_mt_tile& T, const mp_k1mt& a, uint32_t n, mp_mt_walk& W, uint32_t* parent, double* x0) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const u64 last = mp_tile_last(T.tile_of[q], a.n);
-        u64 p = W.p[q];
+        const uint32_t last = mp_tile_last32(T.tile_of[q], n);
+        uint32_t p = W.p[q];
         mp_u64v2 cur = W.cur[q];
         if (W.more[q]) {
 #pragma unroll
@@ -200,32 +219,32 @@ __device__ __forceinline__ void mt_resolve_rest(const mp_mt_tile& T, const mp_k1
                 if (cur.x < T.plt[q] && p < last) { ++p; cur = W.nx[q][k]; }
             }
             if (cur.x < T.plt[q] && p < last) {   // rare: the walk is longer than the rows asked for in advance — the rest by bisection (the first
-                u64 lo = p + 1, hi = last;        // row of (p, last] whose cumulative weight reaches the target, or `last`: mp_resolve_draws' BISECT)
+                uint32_t lo = p + 1, hi = last;   // row of (p, last] whose cumulative weight reaches the target, or `last`: mp_resolve_draws' BISECT)
                 if constexpr (WALKB) {
                     // (a few more rows one at a time first: a bisection is 11 dependent loads, a 5 - 8 row walk fewer)
                     int steps = 0;
                     while (cur.x < T.plt[q] && p < last && steps < MP_WALK_LINEAR - MP_MT_WALK_ROWS) {
                         ++p; ++steps;
-                        cur = mp_ld_row(a.cx_old + p);
+                        cur = mp_ld_row32(a.cx_old, p);
                     }
                     if (!(cur.x < T.plt[q] && p < last)) { lo = p; hi = p; }
                     else lo = p + 1;
                     while (lo < hi) {
-                        const u64 mid = lo + ((hi - lo) >> 1);
-                        if (mp_ld_row(a.cx_old + mid).x >= T.plt[q]) hi = mid;
+                        const uint32_t mid = lo + ((hi - lo) >> 1);
+                        if (mp_ld_row32(a.cx_old, mid).x >= T.plt[q]) hi = mid;
                         else lo = mid + 1;
                     }
                     p = lo;
-                    cur = mp_ld_row(a.cx_old + p);
+                    cur = mp_ld_row32(a.cx_old, p);
                 } else {
                     while (cur.x < T.plt[q] && p < last) {
                         ++p;
-                        cur = mp_ld_row(a.cx_old + p);
+                        cur = mp_ld_row32(a.cx_old, p);
                     }
                 }
             }
         }
-        parent[q] = (uint32_t)p;
+        parent[q] = p;
         x0[q] = __builtin_bit_cast(double, (u64)cur.y);
     }
 }
@@ -233,7 +252,7 @@ __device__ __forceinline__ void mt_resolve_rest(const mp_mt_tile& T, const mp_k1
 // The standard deviates of a lane's two particles (k_propagate's wave-cooperative form, same attempts in the same order):
 // attempt 0 of every deviate straight-line, the rejected ones retried by the wave.  s_it: this wave's 64 words of LDS.
 template <class Model>
-__device__ __forceinline__ void mt_deviates(const Model& model, int ns, const mp_k1mt& a, u64 base, u64 tile, uint32_t* s_it, double* z) {
+__device__ __forceinline__ void mt_deviates(const Model& model, int ns, const mp_k1mt& a, uint32_t n, uint32_t base, uint32_t tile, uint32_t* s_it, double* z) {
     constexpr int NS = Model::MAX_NORMALS;
     constexpr int M = 2 * NS;
 #if MP_MT_PROBE & 1
@@ -248,13 +267,13 @@ __device__ __forceinline__ void mt_deviates(const Model& model, int ns, const mp
     for (int q = 0; q < M; ++q) {
         const int p = q / NS, sidx = q % NS;
         pu[q] = 0.; pr[q] = 1.; att[q] = 1u;
-        if (sidx < ns && base + p < a.n) {
-            const mp_u64x2 b = mp_philox4x32_10((uint32_t)(a.slot_offset + base + p), (uint32_t)a.t,
+        if (sidx < ns && base + (uint32_t)p < n) {
+            const mp_u64x2 b = mp_philox4x32_10((uint32_t)a.slot_offset + base + (uint32_t)p, (uint32_t)a.t,
                                                 ((uint32_t)MP_DOM_MODEL << 16) | model.normal_site(sidx), 0u, a.k0, a.k1);
             if (!mp_polar_attempt(b, &pu[q], &pr[q])) pend |= 1u << q;
         }
     }
-    const u64 wave_slot0 = a.slot_offset + tile * TILE + (u64)wave_ * 128;   // first slot of this wave's lanes
+    const uint32_t wave_slot0 = (uint32_t)a.slot_offset + tile * (uint32_t)TILE + (uint32_t)wave_ * 128u;   // first slot of this wave's lanes (its Philox counter)
     for (uint32_t guard = 0; guard < MP_MAX_ATTEMPTS; ++guard) {
         uint32_t idx[M];
         uint32_t R = 0;   // wave-uniform
@@ -278,7 +297,7 @@ __device__ __forceinline__ void mt_deviates(const Model& model, int ns, const mp
         const bool work = w < R1;
         const uint32_t ent = s_it[work ? w : 0u];
         const uint32_t owner = ent & 63u, oq = (ent >> 8) & 0xFFu, oatt = ent >> 16;
-        const mp_u64x2 b = mp_philox4x32_10((uint32_t)(wave_slot0 + owner * 2 + oq / NS), (uint32_t)a.t,
+        const mp_u64x2 b = mp_philox4x32_10(wave_slot0 + owner * 2u + oq / (uint32_t)NS, (uint32_t)a.t,
                                             ((uint32_t)MP_DOM_MODEL << 16) | model.normal_site((int)(oq % NS)), oatt + k, a.k0, a.k1);
         double u, r;
         const bool acc = mp_polar_attempt(b, &u, &r) && work;
@@ -307,21 +326,24 @@ __device__ __forceinline__ void mt_deviates(const Model& model, int ns, const mp
 #define MP_MT_ORDER 0   // (A/B builds) 0: the deviates of A under the guide gathers, those of B under A's row gathers;  1: both under A's row gathers;
                         // 2, 3: as 1, 0 with B's draws behind A's row requests
 #endif
+#ifndef MP_MT_DEV_EARLY
+#define MP_MT_DEV_EARLY 0   // (A/B builds) 1: the deviates of A in front of the first barrier, under the loads of the tile scalars, whatever MP_MT_ORDER says
+#endif
 
 // `step` for the lane's two slots of one tile: the model functor in Generate mode on the parents' states.  Nothing is stored here
 // (mt_store_tile): between a tile's row gathers and the next tile's, every vector-memory operation would queue behind 4096 gathers.
 template <class Model>
-__device__ __forceinline__ void mt_model(const Model& model, const mp_k1mt& a, const mp_obs_n<Model::DIM_OBS>& obs, u64 base, const double* px0, const double* z,
-                                         double (&lw)[2], double (&xv)[2]) {
+__device__ __forceinline__ void mt_model(const Model& model, const mp_k1mt& a, uint32_t n, const mp_obs_n<Model::DIM_OBS>& obs, uint32_t base, const double* px0,
+                                         const double* z, double (&lw)[2], double (&xv)[2]) {
     constexpr int NS = Model::MAX_NORMALS;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         lw[p] = MP_NEG_INF; xv[p] = 0.;
-        const u64 i = base + (u64)p;
-        if (i < a.n) {
+        const uint32_t i = base + (uint32_t)p;
+        if (i < n) {
             double prev[1] = {px0[p]}, next[1];
             mp_stream rng;
-            rng.k0 = a.k0; rng.k1 = a.k1; rng.slot = (uint32_t)(a.slot_offset + i); rng.step = (uint32_t)a.t;
+            rng.k0 = a.k0; rng.k1 = a.k1; rng.slot = (uint32_t)a.slot_offset + i; rng.step = (uint32_t)a.t;
             mp_generate_handler<Model> g(rng, obs.v, &z[p * NS]);
             model(g, a.t, prev, next);
             lw[p] = 0. + g.weight;   // log_weights.fill(0.) of the resample (particle_filter.rs:114), then += (:81)
@@ -341,11 +363,11 @@ struct mp_mt_lds {
 // A barrier for data exchanged through LDS only: __syncthreads() is also a workgroup-scope fence for global memory, i.e. an
 // s_waitcnt vmcnt(0) — with a tile's row gathers in flight every barrier of the other tile's normalisation would wait for them.
 __device__ __forceinline__ void mt_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void mt_norm_compute(const double (&lw)[2], u64 n, u64 tile, mp_mt_lds& L, unsigned short* s_guide, u64 (&cum)[2], double& m_out,
+__device__ __forceinline__ void mt_norm_compute(const double (&lw)[2], uint32_t n, uint32_t tile, mp_mt_lds& L, unsigned short* s_guide, u64 (&cum)[2], double& m_out,
                                                 u64& W_out, u64& W2_out) {
     constexpr int THREADS = 1024;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u64 base = tile * TILE + (u64)tid * 2;
+    const uint32_t base = tile * (uint32_t)TILE + (uint32_t)tid * 2u;
 #if MP_MT_PROBE & 4
     {
         const u64 q0 = 1ull << 40;
@@ -430,35 +452,39 @@ struct mp_mt_out {
     u64 W, W2;
 };
 // ... and the stores: parents, log-weights, rows, the tile's scalars (everything but the guide, which needs a barrier after its build)
-__device__ __forceinline__ void mt_store_tile(const mp_k1mt& a, u64 tile, const mp_mt_out& o) {
-    const u64 base = tile * TILE + (u64)threadIdx.x * 2;
+__device__ __forceinline__ void mt_store_tile(const mp_k1mt& a, uint32_t n, uint32_t tile, const mp_mt_out& o) {
+    const uint32_t base = tile * (uint32_t)TILE + threadIdx.x * 2u;
+    // (mp_keep32 on each side of a branch: one offset used on both sides is otherwise widened to a 64-bit address in front of it)
     if (!(a.flags & MP_MT_SKIP_PARENT)) {
-        if (base + 1 < a.n) *reinterpret_cast<uint2*>(a.parent + base) = make_uint2(o.par[0], o.par[1]);
-        else if (base < a.n) a.parent[base] = o.par[0];
+        const uint32_t poff = base * (uint32_t)sizeof(uint32_t);
+        if (base + 1u < n) *reinterpret_cast<uint2*>(mp_at32(a.parent, mp_keep32(poff))) = make_uint2(o.par[0], o.par[1]);
+        else if (base < n) *mp_at32(a.parent, mp_keep32(poff)) = o.par[0];
     }
     if (!(a.flags & MP_MT_SKIP_LOGW)) {
-        if (base + 1 < a.n) *reinterpret_cast<double2*>(a.logw + base) = make_double2(o.lw[0], o.lw[1]);
-        else if (base < a.n) a.logw[base] = o.lw[0];
+        const uint32_t loff = base * (uint32_t)sizeof(double);
+        if (base + 1u < n) *reinterpret_cast<double2*>(mp_at32(a.logw, mp_keep32(loff))) = make_double2(o.lw[0], o.lw[1]);
+        else if (base < n) *mp_at32(a.logw, mp_keep32(loff)) = o.lw[0];
     }
     mp_cx* cx = mp_as_global(a.cx_new);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        if (base + j < a.n) {
+        if (base + (uint32_t)j < n) {
             mp_u64v2_ row;
             row.x = o.cum[j];
             row.y = mp_f2u(o.xv[j]);
-            mp_st_stream16<4>(cx + base + j, row);
+            mp_st_stream16<4>(mp_at32(cx, (base + (uint32_t)j) * (uint32_t)sizeof(mp_cx)), row);
         }
     }
     if (threadIdx.x == 0) {
+        const uint32_t toff = tile * 8u;   // (the three arrays of tile scalars hold 8-byte entries)
         if (a.flags & MP_MT_PEEK) {   // (read by another workgroup of THIS launch: agent-scope stores, mt_peek_tail)
-            mp_st_agent(mp_as_global(a.tm_new) + tile, o.m);
-            mp_st_agent(mp_as_global(a.tW_new) + tile, o.W);
-            mp_st_agent(mp_as_global(a.tW2_new) + tile, o.W2);
+            mp_st_agent(mp_at32(mp_as_global(a.tm_new), toff), o.m);
+            mp_st_agent(mp_at32(mp_as_global(a.tW_new), toff), o.W);
+            mp_st_agent(mp_at32(mp_as_global(a.tW2_new), toff), o.W2);
         } else {
-            mp_as_global(a.tm_new)[tile] = o.m;
-            mp_as_global(a.tW_new)[tile] = o.W;
-            mp_as_global(a.tW2_new)[tile] = o.W2;
+            *mp_at32(mp_as_global(a.tm_new), toff) = o.m;
+            *mp_at32(mp_as_global(a.tW_new), toff) = o.W;
+            *mp_at32(mp_as_global(a.tW2_new), toff) = o.W2;
         }
     }
 }
@@ -483,8 +509,9 @@ __device__ __forceinline__ void mt_peek_tail(const mp_k1mt& a, int nt) {
     // nt <= 1024 (the launch condition of this kernel): one tile per thread, its three scalars asked for together — one round trip
     // through the L2, not two (the maximum first, the rest afterwards)
     const bool have = tid < nt;
-    const double mb = have ? mp_ld_agent(tm + tid) : MP_NEG_INF;
-    const u64 Wb = have ? mp_ld_agent(tW + tid) : 0ull, W2b = have ? mp_ld_agent(tW2 + tid) : 0ull;
+    const uint32_t toff = (uint32_t)tid * 8u;
+    const double mb = have ? mp_ld_agent(mp_at32(tm, toff)) : MP_NEG_INF;
+    const u64 Wb = have ? mp_ld_agent(mp_at32(tW, toff)) : 0ull, W2b = have ? mp_ld_agent(mp_at32(tW2, toff)) : 0ull;
     double m = wave_max(mb);
     if (lane == 0) s_red[wave] = m;
     __syncthreads();
@@ -519,18 +546,21 @@ __device__ __forceinline__ void mt_peek_tail(const mp_k1mt& a, int nt) {
     }
 }
 // (MP_MT_REPLAY) only what the first launch of these arguments left out
-__device__ __forceinline__ void mt_store_replay(const mp_k1mt& a, u64 tile, const mp_mt_out& o) {
-    const u64 base = tile * TILE + (u64)threadIdx.x * 2;
-    if (base + 1 < a.n) {
-        *reinterpret_cast<uint2*>(a.parent + base) = make_uint2(o.par[0], o.par[1]);
-        *reinterpret_cast<double2*>(a.logw + base) = make_double2(o.lw[0], o.lw[1]);
-    } else if (base < a.n) {
-        a.parent[base] = o.par[0];
-        a.logw[base] = o.lw[0];
+__device__ __forceinline__ void mt_store_replay(const mp_k1mt& a, uint32_t n, uint32_t tile, const mp_mt_out& o) {
+    const uint32_t base = tile * (uint32_t)TILE + threadIdx.x * 2u;
+    const uint32_t poff = base * (uint32_t)sizeof(uint32_t), loff = base * (uint32_t)sizeof(double);
+    if (base + 1u < n) {
+        *reinterpret_cast<uint2*>(mp_at32(a.parent, mp_keep32(poff))) = make_uint2(o.par[0], o.par[1]);
+        *reinterpret_cast<double2*>(mp_at32(a.logw, mp_keep32(loff))) = make_double2(o.lw[0], o.lw[1]);
+    } else if (base < n) {
+        *mp_at32(a.parent, mp_keep32(poff)) = o.par[0];
+        *mp_at32(a.logw, mp_keep32(loff)) = o.lw[0];
     }
 }
-__device__ __forceinline__ void mt_store_guide(const mp_k1mt& a, u64 tile, const unsigned short* s_guide) {
-    reinterpret_cast<uint32_t*>(mp_as_global(a.guide_new) + tile * GUIDE_N)[threadIdx.x] = reinterpret_cast<const uint32_t*>(s_guide)[threadIdx.x];
+__device__ __forceinline__ void mt_store_guide(const mp_k1mt& a, uint32_t tile, const unsigned short* s_guide) {
+    // (the guide slot of the thread's word: tile * GUIDE_N + 2 * threadIdx.x, two bytes each)
+    const uint32_t goff = tile * (uint32_t)(GUIDE_N * sizeof(unsigned short)) + threadIdx.x * 4u;
+    *reinterpret_cast<uint32_t*>(mp_at32(mp_as_global(a.guide_new), goff)) = reinterpret_cast<const uint32_t*>(s_guide)[threadIdx.x];
 }
 
 // WALKB: walks beyond the rows asked for in advance finish by bisection (collapsed weights: the host picks, mp_pf.hip launch_propagate)
@@ -555,8 +585,9 @@ __global__ __launch_bounds__(1024) void k_propagate_mt(const double* __restrict_
     a.guide_old = mp_as_global(a.guide_old); a.cx_old = mp_as_global(a.cx_old); a.logw = mp_as_global(a.logw); a.parent = mp_as_global(a.parent);
     MP_STAMP_L_DECL;
     MP_STAMP_L(0, 0); MP_STAMP_L(1, 1); MP_STAMP_L(6, 2);
-    const u64 tileA = blockIdx.x, tileB = (u64)blockIdx.x + gridDim.x;
-    const bool hasB = tileB < (u64)pre_nt;   // workgroup-uniform
+    const uint32_t n = (uint32_t)a.n;   // (at most MP_MT_MAX_TILES tiles: the launch condition)
+    const uint32_t tileA = blockIdx.x, tileB = blockIdx.x + gridDim.x;
+    const bool hasB = tileB < (uint32_t)pre_nt;   // workgroup-uniform
 
     // ---- level 1 of the normalisation that was resampled: the job's tile table, ONCE per workgroup, in LDS (k_propagate's
     // arithmetic entry by entry); tile A's Philox block under the loads ----
@@ -565,14 +596,19 @@ __global__ __launch_bounds__(1024) void k_propagate_mt(const double* __restrict_
     double mb = MP_NEG_INF;
     u64 Wb = 0ull, W2b = 0ull;
     if (wave_has) {
-        mb = have_tb ? pre_tm[tb] : MP_NEG_INF;
-        Wb = have_tb ? pre_tW[tb] : 0ull;
-        W2b = (have_tb && blockIdx.x == 0) ? pre_tW2[tb] : 0ull;
+        const uint32_t toff = threadIdx.x * 8u;   // (8-byte entries)
+        mb = have_tb ? *mp_at32(pre_tm, toff) : MP_NEG_INF;
+        Wb = have_tb ? *mp_at32(pre_tW, toff) : 0ull;
+        W2b = (have_tb && blockIdx.x == 0) ? *mp_at32(pre_tW2, toff) : 0ull;
     }
     mp_u64x2 blk;
     blk.a = 0ull; blk.b = 0ull;
-    blk = mp_resample_block((a.slot_offset + tileA * TILE + (u64)tb * 2) >> 1, a.rc, (uint32_t)MP_DOM_RESAMPLE, a.k0, a.k1);
+    // (the block counter is HALF the global slot: the carry of slot_offset + slot out of bit 31 is bit 31 of it — 64 bits)
+    blk = mp_resample_block((a.slot_offset + (u64)(tileA * (uint32_t)TILE + threadIdx.x * 2u)) >> 1, a.rc, (uint32_t)MP_DOM_RESAMPLE, a.k0, a.k1);
     asm volatile("" : "+v"(blk.a), "+v"(blk.b));
+    double zA[2 * NS], zB[2 * NS], px0[2];
+    if constexpr (MP_MT_DEV_EARLY != 0)   // tile A's deviates under the entry loads: no table, no barrier, only this wave's words of s_it
+        mt_deviates<Model>(model, ns, a, n, tileA * (uint32_t)TILE + threadIdx.x * 2u, tileA, s_it[wave1], zA);
     if (wave_has) {
         const double mw = wave_max(mb);
         if (lane1 == 0) s_l1_red[wave1] = mw;
@@ -624,70 +660,69 @@ __global__ __launch_bounds__(1024) void k_propagate_mt(const double* __restrict_
     mp_mt_tile A, B;
     mp_mt_walk WK;
     mp_mt_out oA, oB;
-    double zA[2 * NS], zB[2 * NS], px0[2];
     // (a workgroup without a second tile — the last one of an odd number of tiles — draws and gathers tile A's slots twice and
     // drops the copy: every memory operation up to B's parents is then straight-line code, whose waits the compiler counts exactly)
-    const u64 tileBe = hasB ? tileB : tileA;
+    const uint32_t tileBe = hasB ? tileB : tileA;
     mt_draw<WALKB>(A, tileA, blk, a, pre_nt, s_incl, s_W, s_ratio, Q, nt_over_Q);
     if constexpr (MP_MT_ORDER <= 1) {
-        blk = mp_resample_block((a.slot_offset + tileBe * TILE + (u64)tb * 2) >> 1, a.rc, (uint32_t)MP_DOM_RESAMPLE, a.k0, a.k1);
+        blk = mp_resample_block((a.slot_offset + (u64)(tileBe * (uint32_t)TILE + threadIdx.x * 2u)) >> 1, a.rc, (uint32_t)MP_DOM_RESAMPLE, a.k0, a.k1);
         mt_draw<WALKB>(B, tileBe, blk, a, pre_nt, s_incl, s_W, s_ratio, Q, nt_over_Q);
     }
     MP_STAMP_L(18, 0);
-    if constexpr (MP_MT_ORDER == 0 || MP_MT_ORDER == 3) mt_deviates<Model>(model, ns, a, A.base, tileA, s_it[wave1], zA);   // under the guide gathers
+    if constexpr (MP_MT_DEV_EARLY == 0 && (MP_MT_ORDER == 0 || MP_MT_ORDER == 3)) mt_deviates<Model>(model, ns, a, n, A.base, tileA, s_it[wave1], zA);   // under the guide gathers
     MP_STAMP_L(19, 0);
     asm volatile("" : "+v"(A.g[0]), "+v"(A.g[1]));
-    mt_rows(A, a);
+    mt_rows(A, a, n);
     MP_STAMP_L(2, 0);
     if constexpr (MP_MT_ORDER >= 2) {   // B's draws (and its guide gathers) only now: A's row gathers are asked for as early as they can be
-        blk = mp_resample_block((a.slot_offset + tileBe * TILE + (u64)tb * 2) >> 1, a.rc, (uint32_t)MP_DOM_RESAMPLE, a.k0, a.k1);
+        blk = mp_resample_block((a.slot_offset + (u64)(tileBe * (uint32_t)TILE + threadIdx.x * 2u)) >> 1, a.rc, (uint32_t)MP_DOM_RESAMPLE, a.k0, a.k1);
         mt_draw<WALKB>(B, tileBe, blk, a, pre_nt, s_incl, s_W, s_ratio, Q, nt_over_Q);
     }
-    if constexpr (MP_MT_ORDER == 1 || MP_MT_ORDER == 2) mt_deviates<Model>(model, ns, a, A.base, tileA, s_it[wave1], zA);
-    mt_deviates<Model>(model, ns, a, B.base, tileBe, s_it[wave1], zB);                                  // under A's row gathers
+    if constexpr (MP_MT_DEV_EARLY == 0 && (MP_MT_ORDER == 1 || MP_MT_ORDER == 2)) mt_deviates<Model>(model, ns, a, n, A.base, tileA, s_it[wave1], zA);
+    mt_deviates<Model>(model, ns, a, n, B.base, tileBe, s_it[wave1], zB);                                  // under A's row gathers
     MP_STAMP_L(22, 0);
-    mt_resolve_first(A, a, WK);           // A's rows have landed: parents, first walk loads
+    mt_resolve_first(A, a, n, WK);           // A's rows have landed: parents, first walk loads
 #if MP_MT_WALK_BARRIER
     // every wave's walks of A are over before any wave asks for B's rows: the CU serves vector-memory operations in order, ACROSS
     // waves, so a late wave's walk loads would otherwise wait behind the early waves' 64-lane gathers for B (and A's normalisation,
     // behind its first barrier, for that wave)
-    mt_resolve_rest<WALKB>(A, a, WK, oA.par, px0);
+    mt_resolve_rest<WALKB>(A, a, n, WK, oA.par, px0);
     MP_STAMP_L(23, 0);
     mt_lds_barrier();
     asm volatile("" : "+v"(B.g[0]), "+v"(B.g[1]));
-    mt_rows(B, a);
+    mt_rows(B, a, n);
 #else
     asm volatile("" : "+v"(B.g[0]), "+v"(B.g[1]));   // (B's start rows are computed here, not hoisted to where its guide cells were asked for)
-    mt_rows(B, a);                        // B's row pairs go out behind them
+    mt_rows(B, a, n);                        // B's row pairs go out behind them
     MP_STAMP_L(23, 0);
-    mt_resolve_rest<WALKB>(A, a, WK, oA.par, px0);
+    mt_resolve_rest<WALKB>(A, a, n, WK, oA.par, px0);
 #endif
     MP_STAMP_L(25, 0);
-    mt_model<Model>(model, a, obs, A.base, px0, zA, oA.lw, oA.xv);
+    mt_model<Model>(model, a, n, obs, A.base, px0, zA, oA.lw, oA.xv);
     MP_STAMP_L(26, 0);
     const bool replay = (a.flags & MP_MT_REPLAY) != 0;   // workgroup-uniform
-    if (!replay) mt_norm_compute(oA.lw, a.n, tileA, s_norm, s_guideA, oA.cum, oA.m, oA.W, oA.W2);   // LDS and registers only: under B's row gathers
+    if (!replay) mt_norm_compute(oA.lw, n, tileA, s_norm, s_guideA, oA.cum, oA.m, oA.W, oA.W2);   // LDS and registers only: under B's row gathers
     MP_STAMP_L(20, 0);
-    mt_resolve_first(B, a, WK);
-    mt_resolve_rest<WALKB>(B, a, WK, oB.par, px0);
+    mt_resolve_first(B, a, n, WK);
+    mt_resolve_rest<WALKB>(B, a, n, WK, oB.par, px0);
     if (replay) {
-        mt_store_replay(a, tileA, oA);
+        mt_store_replay(a, n, tileA, oA);
         if (hasB) {
-            mt_model<Model>(model, a, obs, B.base, px0, zB, oB.lw, oB.xv);
-            mt_store_replay(a, tileB, oB);
+            mt_model<Model>(model, a, n, obs, B.base, px0, zB, oB.lw, oB.xv);
+            mt_store_replay(a, n, tileB, oB);
         }
     } else if (hasB) {
         MP_STAMP_L(27, 0);
-        mt_store_tile(a, tileA, oA);      // the vector-memory path is free again: A's stores under B's arithmetic
-        mt_model<Model>(model, a, obs, B.base, px0, zB, oB.lw, oB.xv);
+        mt_store_tile(a, n, tileA, oA);      // the vector-memory path is free again: A's stores under B's arithmetic
+        mt_model<Model>(model, a, n, obs, B.base, px0, zB, oB.lw, oB.xv);
         MP_STAMP_L(28, 0);
-        mt_norm_compute(oB.lw, a.n, tileB, s_norm, s_guideB, oB.cum, oB.m, oB.W, oB.W2);
-        mt_store_tile(a, tileB, oB);
+        mt_norm_compute(oB.lw, n, tileB, s_norm, s_guideB, oB.cum, oB.m, oB.W, oB.W2);
+        mt_store_tile(a, n, tileB, oB);
         __syncthreads();                  // both guides are complete
         mt_store_guide(a, tileA, s_guideA);
         mt_store_guide(a, tileB, s_guideB);
     } else {
-        mt_store_tile(a, tileA, oA);
+        mt_store_tile(a, n, tileA, oA);
         __syncthreads();
         mt_store_guide(a, tileA, s_guideA);
     }

@@ -735,6 +735,28 @@ __device__ __forceinline__ u64 mp_tile_last(uint32_t row, u64 n) {
     const u64 tend = (((u64)row / TILE) + 1) * TILE;
     return (tend < n ? tend : n) - 1;      // last row of the tile
 }
+// 32-bit forms for kernels whose launch condition bounds the job (k_propagate_mt, mp_pf_k1mt.h: at most 1024 tiles, so that every row
+// index and every byte offset into a per-row or per-tile array fits a uint32_t).  A launch-constant base pointer plus a 32-bit BYTE
+// offset is what the global_* instructions take as `v_off, s[base:base+1]`: the address costs no 64-bit vector arithmetic and one
+// VGPR instead of two.  The offset is formed in 32 bits by the caller's promise that it fits — nothing is widened before the add.
+template <class T>
+__device__ __forceinline__ T* mp_at32(T* base, uint32_t byte_off) {
+    return (T*)((const char*)base + byte_off);
+}
+// A 32-bit offset the compiler may not look through (an empty statement: no instruction).  For an offset that is a select against a
+// constant (`want ? row : 0`) or that is used on both sides of a branch: left transparent, the first becomes a 64-bit select between
+// two ADDRESSES and the second one widened address computed in front of the branch — either way the access is back to a VGPR pair.
+__device__ __forceinline__ uint32_t mp_keep32(uint32_t v) {
+    asm("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ mp_u64v2 mp_ld_row32(const mp_cx* base, uint32_t row) {
+    return *reinterpret_cast<const mp_u64v2*>(mp_at32(base, row * (uint32_t)sizeof(mp_cx)));
+}
+__device__ __forceinline__ uint32_t mp_tile_last32(uint32_t row, uint32_t n) {   // mp_tile_last: min(tile end, n) - 1, n >= 1
+    const uint32_t tl = row | (uint32_t)(TILE - 1);
+    return tl < n - 1u ? tl : n - 1u;
+}
 // A slot of a SHARDED filter whose offspring arrives from another rank has no draw to look up: its entry in the start-row array
 // is MP_DRAW_RECV | the index of its row {state[dim], parent's global slot id} in the exchange buffer (`rows`, rows of `rw`
 // doubles); the "parent" handed on keeps the flag, so that the consumer knows where the state is.
