@@ -162,6 +162,28 @@ int32_t mp_pf_read_trajectories(mp_pf* h, uint64_t first, uint64_t count, double
  * computes afterwards.  Needs MP_PF_RECORD_HISTORY (else MP_ERR_STATE; also before init_step).  All log-weights -inf:
  * MP_ERR_DEGENERATE.  One shard of a larger world, or a dim_state other than 1, 2, 4, 16: MP_ERR_UNSUPPORTED. */
 int32_t mp_pf_path_moments(mp_pf* h, double* mean_out, double* var_out, uint64_t* distinct_out, int32_t* t_steps);
+/* The FORECAST: DynUnfold::update with ArgDiff::Extend and EMPTY constraint tries for the new steps (modppl/src/modeling/
+ * dynunfold.rs:66-100) runs the kernel from each trace's last state, sample_at's unconstrained arm draws every site and the weight is 0;
+ * done to every trace of the filter that is "where will the state be in H steps, and what will I observe".  With H = horizon >= 1 and
+ * T = mp_pf_time: for k = 0 .. H-1 slot i runs the model kernel in Simulate mode (every site drawn, the observed ones too) at time T + k
+ * from its own current state (k = 0) or its previous forecast state: v_i(k) [dim_state], y_i(k) [dim_obs].  Philox slot = the global
+ * slot, Philox step = kernel time = T + k: the counters mp_pf_step would use, so the forecast states are bit for bit the states the next
+ * H unresampled steps propose (whatever they observe), and after init_step slot i's forecast is trace i of
+ * mp_unfold_simulate(model, args0, 1 + H, n, seed) at steps 1 .. H.  DESIGN.md section 4, "Forecast".
+ *   mp_pf_forecast_paths: the paths of slots first .. first + count - 1 -> states_out[count][H][dim_state], obs_out[count][H][dim_obs]
+ *     (either may be NULL, not both).  Per slot: works on any shard.
+ *   mp_pf_forecast_moments: with the weights a_i of mp_pf_moments,
+ *     state_mean_out[k][j] = sum_i a_i v_ij(k) / sum_i a_i;  state_var_out[k][j] = sum_i a_i (v_ij(k) - mean_kj)^2 / sum_i a_i
+ *     (population form, marginal variances only), and the same over y for obs_mean_out / obs_var_out [H][dim_obs]; any may be NULL, not
+ *     all.  Every sum is the pairwise tree over GLOBAL slot ids of DESIGN.md section 4.  Nothing of size n * H is stored: the variance
+ *     pass simulates again from the same counters.  All log-weights -inf: MP_ERR_DEGENERATE.  One shard of a larger world, or a
+ *     dim_state other than 1, 2, 4, 16: MP_ERR_UNSUPPORTED.
+ * Both are synchronous on the handle's stream, bring the handle to a readable state exactly as mp_pf_moments does and change nothing the
+ * filter computes afterwards (no state, weight, parent, counter, time or history event).  Before init_step: MP_ERR_STATE.  horizon < 1,
+ * first + count > n_particles or every output NULL: MP_ERR_INVALID_ARG.  MP_MODEL_HMM: MP_ERR_UNSUPPORTED (the reference's HMM has no
+ * simulate, as for mp_unfold_simulate). */
+int32_t mp_pf_forecast_paths(mp_pf* h, int32_t horizon, uint64_t first, uint64_t count, double* states_out, double* obs_out);
+int32_t mp_pf_forecast_moments(mp_pf* h, int32_t horizon, double* state_mean_out, double* state_var_out, double* obs_mean_out, double* obs_var_out);
 /* Number of Unfold steps taken so far (trace.args.0). */
 int32_t mp_pf_time(mp_pf* h, int64_t* out);
 /* Whole filter in one call: init_step on obs[0], then for t=1..T-1 {step; resample} with a

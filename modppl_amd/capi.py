@@ -33,7 +33,7 @@ MP_MH_PROPOSAL_POINTED_DRIFT = 3
 SYMBOLS = [
     "mp_last_error", "mp_device_count", "mp_pf_create", "mp_pf_init_step", "mp_pf_step", "mp_pf_effective_sample_size",
     "mp_pf_resample", "mp_pf_resample_if_ess_below", "mp_pf_log_marginal_likelihood_estimate", "mp_pf_read_state", "mp_pf_read_log_weights",
-    "mp_pf_read_parents", "mp_pf_moments", "mp_pf_read_trajectory", "mp_pf_read_trajectories", "mp_pf_path_moments", "mp_pf_time", "mp_pf_run", "mp_pf_synchronize", "mp_pf_destroy",
+    "mp_pf_read_parents", "mp_pf_moments", "mp_pf_read_trajectory", "mp_pf_read_trajectories", "mp_pf_path_moments", "mp_pf_forecast_paths", "mp_pf_forecast_moments", "mp_pf_time", "mp_pf_run", "mp_pf_synchronize", "mp_pf_destroy",
     "mp_pf_set_timing", "mp_pf_get_timing", "mp_pf_region_begin", "mp_pf_region_end", "mp_pf_last_propagate_form", "mp_unfold_simulate", "mp_importance_resampling", "mp_importance_sampling",
     "mp_pf_shard_bind_tiles", "mp_pf_shard_tiles_packed", "mp_pf_shard_route_fixed", "mp_pf_shard_resolve_fixed", "mp_pf_shard_commit_fixed", "mp_pf_shard_query_packed",
     "mp_pf_shard_owned_count", "mp_pf_shard_owned_expand", "mp_pf_shard_owned_commit", "mp_pf_shard_owned_count_expand",
@@ -152,6 +152,8 @@ def _load_so(so):
     L.mp_pf_read_trajectory.argtypes = [p, u64, dp, C.POINTER(i32)]
     L.mp_pf_read_trajectories.argtypes = [p, u64, u64, dp, C.POINTER(i32)]
     L.mp_pf_path_moments.argtypes = [p, dp, dp, C.POINTER(u64), C.POINTER(i32)]
+    L.mp_pf_forecast_paths.argtypes = [p, i32, u64, u64, dp, dp]
+    L.mp_pf_forecast_moments.argtypes = [p, i32, dp, dp, dp, dp]
     L.mp_pf_time.argtypes = [p, C.POINTER(i64)]
     L.mp_pf_run.argtypes = [p, dp, dp, i32, i32]
     L.mp_pf_synchronize.argtypes = [p]

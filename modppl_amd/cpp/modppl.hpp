@@ -108,6 +108,25 @@ public:
         check(mp_pf_path_moments(h_, m.mean.data(), var ? m.var.data() : nullptr, distinct ? m.distinct.data() : nullptr, &steps));
         return m;
     }
+    // the forecast over the next `horizon` steps (mp_pf_forecast_moments / _paths; dynunfold.rs:66-100 with empty constraints): every
+    // slot runs the model in Simulate mode from its own state with the counters the next steps would use.  Moments: weighted mean and
+    // population variance of the state [H][dim_state] and of the observation [H][dim_obs], reduced on the device; empty where not asked for
+    struct Forecast { std::vector<double> state_mean, state_var, obs_mean, obs_var; };
+    Forecast forecast(int32_t horizon, bool var = true, bool obs = true) {
+        const size_t H = horizon > 0 ? (size_t)horizon : 0, hd = H * (size_t)model_.dim_state, ho = H * (size_t)model_.dim_obs;
+        Forecast f{std::vector<double>(hd), std::vector<double>(var ? hd : 0), std::vector<double>(obs ? ho : 0), std::vector<double>(obs && var ? ho : 0)};
+        check(mp_pf_forecast_moments(h_, horizon, f.state_mean.data(), var ? f.state_var.data() : nullptr, obs ? f.obs_mean.data() : nullptr,
+                                     obs && var ? f.obs_var.data() : nullptr));
+        return f;
+    }
+    // the predictive paths of slots first .. first + count - 1: states [count][H][dim_state], obs [count][H][dim_obs], row-major
+    struct ForecastPaths { std::vector<double> states, obs; };
+    ForecastPaths forecast_paths(int32_t horizon, uint64_t first, uint64_t count) {
+        const size_t H = horizon > 0 ? (size_t)horizon : 0;
+        ForecastPaths p{std::vector<double>(count * H * (size_t)model_.dim_state), std::vector<double>(count * H * (size_t)model_.dim_obs)};
+        check(mp_pf_forecast_paths(h_, horizon, first, count, p.states.data(), p.obs.data()));
+        return p;
+    }
     std::vector<double> log_weights() {
         std::vector<double> w(n_);
         check(mp_pf_read_log_weights(h_, w.data()));

@@ -72,6 +72,7 @@ int32_t mp_set_error(int32_t code, const std::string& msg) { return mp_fail(code
 #include "mp_pf_shard_kernels.h"
 #define MP_MOMENTS_PF
 #include "mp_moments.h"   // mp_pf_moments: the tree reduction and its kernels (after every existing kernel)
+#include "mp_forecast.h"  // mp_pf_forecast_paths / _moments: Simulate mode from the cloud, through the same trees
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -142,6 +143,10 @@ struct ModelOps {
     virtual int propagate(const PropagateArgs& a) const = 0;   // -> MP_K1_FORM_* of the kernel it launched
     virtual int n_normals(long long t) const = 0;
     virtual void simulate(u64 n, uint32_t k0, uint32_t k1, int n_steps, const mp_state0& s0, double* states, double* obs, hipStream_t st) const = 0;
+    // mp_forecast.h: the window [first, first + count) of predictive paths; pass 1 or 2 of the predictive moments (nb workgroups,
+    // res = {m, S[H][C], A, mean[H][C], ...} as in launch_path_pass, partials into `out`)
+    virtual void forecast_paths(const mp_forecast_args& f, u64 first, u64 count, double* states, double* obs, hipStream_t st) const = 0;
+    virtual void forecast_moments(const mp_forecast_args& f, int pass, unsigned nb, const double* lw, double* res, double* out, hipStream_t st) const = 0;
 };
 // light kernels (few registers) run 1024 threads x 2 particles per tile: twice the waves in flight for the same 2048-slot tile.  The
 // launch shape, can_draw and launch_propagate's walk rule (ModelOps::light) all come from this one trait.
@@ -164,6 +169,18 @@ struct ModelOpsT : ModelOps {
     }
     void simulate(u64 n, uint32_t k0, uint32_t k1, int n_steps, const mp_state0& s0, double* states, double* obs, hipStream_t st) const override {
         hipLaunchKernelGGL(k_simulate<Model>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, model, n, k0, k1, n_steps, s0, states, obs);
+    }
+    void forecast_paths(const mp_forecast_args& f, u64 first, u64 count, double* states, double* obs, hipStream_t st) const override {
+        hipLaunchKernelGGL(k_forecast_paths<Model>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, model, f, first, count, states, obs);
+    }
+    void forecast_moments(const mp_forecast_args& f, int pass, unsigned nb, const double* lw, double* res, double* out, hipStream_t st) const override {
+        const size_t HC = (size_t)f.horizon * (Model::DIM_STATE + Model::DIM_OBS);
+        if (pass == 1)
+            hipLaunchKernelGGL((k_forecast_mom<Model, false>), dim3(nb), dim3(MOM_THREADS), 0, st, model, f, lw, (const double*)res, (const double*)nullptr,
+                               (double*)nullptr, out);
+        else
+            hipLaunchKernelGGL((k_forecast_mom<Model, true>), dim3(nb), dim3(MOM_THREADS), 0, st, model, f, lw, (const double*)res, (const double*)(res + 1),
+                               res + 2 + HC, out);
     }
     int propagate(const PropagateArgs& a) const override {
         const int k1t = k1_threads_override();   // A/B measurements
@@ -285,6 +302,7 @@ struct mp_pf {
     std::unique_ptr<mp_shard_native_state, mp_shard_native_delete> native;   // buffers and bookkeeping of mp_pf_shard_resample
     u64 n = 0, n_global = 0, slot_offset = 0, seed = 0;
     uint32_t flags = 0;
+    int model_kind = 0;   // mp_model_desc::kind
     int device = 0;
     int S = 0;
     int nt = 0;  // tiles of this handle (== K1 grid)
@@ -430,6 +448,14 @@ struct mp_pf {
     mp_pinned<double> path_host;
     mp_dev<uint32_t> path_bits;            // [T][ceil(n / 32)]
     size_t path_cap_t = 0, path_bits_cap_t = 0;   // the T they hold
+    // mp_pf_forecast_moments, sized on first use and grown with the horizon: the same three for H * (dim_state + dim_obs) columns (+ A);
+    // mp_pf_forecast_paths: the device side of one chunk of the window ([chunk][H][dim_state], [chunk][H][dim_obs])
+    mp_dev<double> fc_buf[2];
+    mp_dev<double> fc_res;                 // {m, S[H][C], A, mean[H][C], V[H][C]}
+    mp_pinned<double> fc_host;
+    size_t fc_cap_h = 0;                   // the H they hold
+    mp_dev<double> fc_paths[2];            // states, observations
+    size_t fc_paths_cap[2] = {0, 0};       // (doubles)
     // host-side filter state
     long long t = 0;  // Unfold steps taken (trace.args.0)
     uint32_t resample_count = 0;
@@ -860,6 +886,7 @@ int32_t mp_pf_create(const mp_model_desc* model, uint64_t n_particles, uint64_t 
     struct Cleanup { void operator()(mp_pf* p) const { (void)mp_pf_destroy(p); } };   // an early return frees what was allocated so far
     std::unique_ptr<mp_pf, Cleanup> h(new mp_pf());
     MPCK(make_model(model, h->ops));
+    h->model_kind = model->kind;
     h->n = n_particles;
     h->n_global = shard ? shard->n_global : n_particles;
     h->slot_offset = shard ? shard->slot_offset : 0;
@@ -2018,6 +2045,121 @@ int32_t mp_pf_path_moments(mp_pf* h, double* mean_out, double* var_out, uint64_t
     if (var_out)
         for (size_t c = 0; c < TD; ++c) var_out[c] = r[2 + 2 * TD + c] / A;
     if (distinct_out) memcpy(distinct_out, r + 2 + 3 * TD, sizeof(uint64_t) * (size_t)T);
+    return MP_OK;
+}
+
+// The forecast (mp_forecast.h; DESIGN.md section 4, "Forecast"): DynUnfold::update with ArgDiff::Extend and EMPTY constraints for the new
+// steps (modppl/src/modeling/dynunfold.rs:66-100) — every site of the next `horizon` kernel calls drawn, from each slot's own state,
+// with the Philox counters the next steps would use.  Both calls bring the handle to a readable state as mp_pf_moments does and change
+// nothing the filter computes afterwards: no state, weight, parent, counter, time or history event.
+static int32_t forecast_begin(mp_pf* h, const char* who, int32_t horizon, mp_forecast_args& f) {
+    if (!h) return mp_fail(MP_ERR_INVALID_ARG, "null handle");
+    if (h->model_kind == MP_MODEL_HMM) return mp_fail(MP_ERR_UNSUPPORTED, "the reference's HMM has no simulate (tests/hmm/model.rs: unimplemented)");
+    if (!h->initialised) return mp_fail(MP_ERR_STATE, std::string(who) + " before init_step");
+    if (horizon < 1) return mp_fail(MP_ERR_INVALID_ARG, std::string(who) + ": horizon must be at least 1");
+    f.n = h->n; f.slot_offset = h->slot_offset;
+    f.k0 = (uint32_t)h->seed; f.k1 = (uint32_t)(h->seed >> 32);
+    f.t = h->t;
+    f.horizon = horizon;
+    return MP_OK;
+}
+// a grow-only device buffer of at least `want` doubles
+static int32_t fc_grow(mp_dev<double>& buf, size_t& cap, size_t want) {
+    if (cap >= want) return MP_OK;
+    cap = 0;
+    HIPCK(mp_hipMalloc(buf, want));
+    cap = want;
+    return MP_OK;
+}
+
+int32_t mp_pf_forecast_paths(mp_pf* h, int32_t horizon, uint64_t first, uint64_t count, double* states_out, double* obs_out) {
+    mp_forecast_args f;
+    MPCK(forecast_begin(h, "forecast_paths", horizon, f));
+    if (!states_out && !obs_out) return mp_fail(MP_ERR_INVALID_ARG, "forecast_paths: every output is null");
+    if (first > h->n || count > h->n - first) return mp_fail(MP_ERR_INVALID_ARG, "forecast_paths: first + count exceeds the number of particles");
+    HIPCK(hipSetDevice(h->device));
+    MPCK(materialize(h));
+    MPCK(ensure_x(h));
+    MPCK(ensure_lazy(h));
+    f.x = h->x[h->cur];
+    const size_t D = (size_t)h->ops->dim_state, DO = (size_t)h->ops->dim_obs, H = (size_t)horizon;
+    // slots per launch: 2^22 doubles of states + observations on the device at a time, but never fewer than 2^16 slots (a launch that
+    // fills the device), whatever the window and the horizon
+    const u64 chunk = std::max<u64>(1, std::min<u64>(count, std::max<u64>((u64)1 << 16, ((u64)1 << 22) / (H * (D + DO)))));
+    if (states_out) MPCK(fc_grow(h->fc_paths[0], h->fc_paths_cap[0], (size_t)chunk * H * D));
+    if (obs_out) MPCK(fc_grow(h->fc_paths[1], h->fc_paths_cap[1], (size_t)chunk * H * DO));
+    double* dx = states_out ? h->fc_paths[0].get() : nullptr;
+    double* dy = obs_out ? h->fc_paths[1].get() : nullptr;
+    hipError_t e = hipSuccess;
+    for (u64 c0 = 0; c0 < count && e == hipSuccess; c0 += chunk) {
+        const u64 cn = std::min<u64>(chunk, count - c0);
+        h->ops->forecast_paths(f, first + c0, cn, dx, dy, h->stream);
+        e = hipGetLastError();
+        if (e == hipSuccess && dx) e = hipMemcpyAsync(states_out + (size_t)c0 * H * D, dx, sizeof(double) * (size_t)cn * H * D, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess && dy) e = hipMemcpyAsync(obs_out + (size_t)c0 * H * DO, dy, sizeof(double) * (size_t)cn * H * DO, hipMemcpyDeviceToHost, h->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return mp_fail(MP_ERR_HIP, std::string("mp_pf_forecast_paths: ") + hipGetErrorString(e));
+    return MP_OK;
+}
+
+// As in mp_pf_moments every launch is enqueued before the one wait.  The kernels reduce the state and the observation columns alike
+// (Simulate mode draws the observations anyway); what the caller did not ask for is not copied out.
+int32_t mp_pf_forecast_moments(mp_pf* h, int32_t horizon, double* state_mean_out, double* state_var_out, double* obs_mean_out, double* obs_var_out) {
+    mp_forecast_args f;
+    MPCK(forecast_begin(h, "forecast_moments", horizon, f));
+    if (!state_mean_out && !state_var_out && !obs_mean_out && !obs_var_out) return mp_fail(MP_ERR_INVALID_ARG, "forecast_moments: every output is null");
+    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_forecast_moments: one shard of a larger world (n_global != n_particles); the moments of a sharded job need an all-reduce of the max and an all-gather of the partials");
+    const int d = h->ops->dim_state, dobs = h->ops->dim_obs;
+    if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_forecast_moments: no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
+    HIPCK(hipSetDevice(h->device));
+    MPCK(materialize(h));
+    MPCK(ensure_x(h));
+    MPCK(ensure_lazy(h));
+    f.x = h->x[h->cur];
+    const int R = d <= 4 ? 8 : 4;   // mom_run<D>::R
+    const size_t C = (size_t)(d + dobs), H = (size_t)horizon, HC = H * C;
+    const u64 nb = (h->n + (u64)MOM_THREADS * R - 1) / ((u64)MOM_THREADS * R);
+    const u64 nb_max = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);   // (<= nb)
+    const u64 nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
+    const size_t n_res = 2 + 3 * HC;
+    if (h->fc_cap_h < H) {
+        const size_t cap = std::max<size_t>(16, 2 * H), cols = cap * C + 1;
+        h->fc_cap_h = 0;
+        HIPCK(mp_hipMalloc(h->fc_buf[0], cols * nb));
+        HIPCK(mp_hipMalloc(h->fc_buf[1], cols * nn));
+        HIPCK(mp_hipHostMalloc(h->fc_host, 2 + 3 * cap * C));
+        HIPCK(mp_hipMalloc(h->fc_res, 2 + 3 * cap * C));
+        h->fc_cap_h = cap;
+    }
+    double* const buf[2] = {h->fc_buf[0].get(), h->fc_buf[1].get()};
+    double* res = h->fc_res;
+    const bool want_var = state_var_out || obs_var_out;
+    hipLaunchKernelGGL(k_mom_max0, dim3((unsigned)nb_max), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->logw, buf[0]);
+    mom_close<mom_max>(h->stream, buf, nb_max, 1, res);
+    for (int pass = 1; pass <= (want_var ? 2 : 1); ++pass) {
+        h->ops->forecast_moments(f, pass, (unsigned)nb, h->logw, res, buf[0], h->stream);
+        path_close(h->stream, buf, nb, pass == 1 ? HC + 1 : HC, pass == 1 ? res + 1 : res + 2 + 2 * HC);
+    }
+    MPCK(check_launch("mp_pf_forecast_moments kernels"));
+    HIPCK(hipMemcpyAsync(h->fc_host, res, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(stream_wait(h->stream));
+    const double* r = h->fc_host;
+    if (r[0] == -MP_INF) return mp_fail_degenerate();
+    const double A = r[1 + HC];
+    // without a variance pass nobody has formed the means on the device: the same IEEE division here
+    for (size_t k = 0; k < H; ++k)
+        for (size_t c = 0; c < C; ++c) {
+            const size_t col = k * C + c;
+            const double mean = want_var ? r[2 + HC + col] : r[1 + col] / A;
+            const bool is_state = c < (size_t)d;
+            double* mo = is_state ? state_mean_out : obs_mean_out;
+            double* vo = is_state ? state_var_out : obs_var_out;
+            const size_t o = is_state ? k * d + c : k * dobs + (c - d);
+            if (mo) mo[o] = mean;
+            if (vo) vo[o] = r[2 + 2 * HC + col] / A;
+        }
     return MP_OK;
 }
 

@@ -685,26 +685,40 @@ __global__ __launch_bounds__(1024) void k_build_table(const double* tile_m, cons
 
 // GenFn::simulate over an Unfold model (dynunfold.rs:22-39): one lane = one trace of n_steps kernel calls, every site
 // sampled.  states[i][t][d], obs[i][t][dim_obs] (particle-major, like everything that crosses the ABI).
+// One kernel call in Simulate mode at time t (= the Philox step; rng.k0 / k1 / slot are the caller's): prev -> next, observations -> y.
+template <class Model>
+__device__ __forceinline__ void mp_simulate_step(const Model& model, mp_stream& rng, long long t, const double* prev, double* next, double* y) {
+    rng.step = (uint32_t)t;
+    for (int j = 0; j < Model::DIM_OBS; ++j) y[j] = 0.;
+    mp_simulate_handler<Model> g(rng, y);
+    model(g, t, prev, next);
+}
+// One trace: n_steps kernel calls at times t0 .. t0 + n_steps - 1 from the state `prev` (left at the last state).  xs [n_steps][D] and
+// ys [n_steps][DO] are the trace's rows; either may be null (mp_pf_forecast_paths).  k_simulate starts it at time 0 from args0,
+// k_forecast_paths (mp_forecast.h) at the filter's time from the slot's own state.
+template <class Model>
+__device__ __forceinline__ void mp_simulate_trace(const Model& model, mp_stream& rng, long long t0, int n_steps, double* prev,
+                                                  double* __restrict__ xs, double* __restrict__ ys) {
+    constexpr int D = Model::DIM_STATE, DO = Model::DIM_OBS;
+    double next[D], y[DO];
+    for (int s = 0; s < n_steps; ++s) {
+        mp_simulate_step(model, rng, t0 + s, prev, next, y);
+        for (int d = 0; d < D; ++d) prev[d] = next[d];
+        if (xs) for (int d = 0; d < D; ++d) xs[(u64)s * D + d] = next[d];
+        if (ys) for (int j = 0; j < DO; ++j) ys[(u64)s * DO + j] = y[j];
+    }
+}
 template <class Model>
 __global__ __launch_bounds__(256) void k_simulate(Model model, u64 n, uint32_t k0, uint32_t k1, int n_steps, mp_state0 s0,
                                                   double* __restrict__ states, double* __restrict__ obs) {
     constexpr int D = Model::DIM_STATE, DO = Model::DIM_OBS;
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    double prev[D], next[D], y[DO];
+    double prev[D];
     for (int d = 0; d < D; ++d) prev[d] = s0.v[d];
     mp_stream rng;
     rng.k0 = k0; rng.k1 = k1; rng.slot = (uint32_t)i;
-    for (int t = 0; t < n_steps; ++t) {
-        rng.step = (uint32_t)t;
-        for (int j = 0; j < DO; ++j) y[j] = 0.;
-        mp_simulate_handler<Model> g(rng, y);
-        model(g, (long long)t, prev, next);
-        double* xs = states + (i * (u64)n_steps + (u64)t) * D;
-        double* ys = obs + (i * (u64)n_steps + (u64)t) * DO;
-        for (int d = 0; d < D; ++d) { xs[d] = next[d]; prev[d] = next[d]; }
-        for (int j = 0; j < DO; ++j) ys[j] = y[j];
-    }
+    mp_simulate_trace(model, rng, 0, n_steps, prev, states + i * (u64)n_steps * D, obs + i * (u64)n_steps * DO);
 }
 
 constexpr uint32_t MP_MAX_ATTEMPTS = 1u << 16;   // exit condition of every retry loop (acceptance pi/4: never reached)

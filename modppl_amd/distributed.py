@@ -188,6 +188,16 @@ class HipShardEngine:
         capi.check(self._L.mp_pf_moments(self._h, mean.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_double)) if cov else None))
         return mean, c
 
+    def forecast(self, horizon, var=True, obs=True):
+        from .inference import _forecast
+
+        return _forecast(self._L, self._h, self.model, horizon, var, obs)
+
+    def forecast_paths(self, horizon, first=0, count=None):
+        from .inference import _forecast_paths
+
+        return _forecast_paths(self._L, self._h, self.model, horizon, first, self.n - int(first) if count is None else count)
+
     def parents(self):
         p = np.empty(self.n, dtype=np.uint32)
         capi.check(self._L.mp_pf_read_parents(self._h, p.ctypes.data_as(C.POINTER(C.c_uint32))))
@@ -696,6 +706,16 @@ class ShardedParticleSystem:
         larger world raises the library's MP_ERR_UNSUPPORTED (the sharded form needs an all-reduce of the max log-weight and an
         all-gather of the tile partials)."""
         return self.engine.moments(cov)
+
+    def forecast(self, horizon, var=True, obs=True):
+        """-> (state mean, state var, obs mean, obs var) over the next `horizon` steps (ParticleSystem.forecast).  A world of one only,
+        as `moments`: one shard of a larger world raises the library's MP_ERR_UNSUPPORTED."""
+        return self.engine.forecast(horizon, var, obs)
+
+    def forecast_paths(self, horizon, first=0, count=None):
+        """-> (states [count, H, dim_state], obs [count, H, dim_obs]) of THIS rank's slots first .. first + count - 1
+        (ParticleSystem.forecast_paths; per slot, keyed by the global slot: works on any shard)."""
+        return self.engine.forecast_paths(horizon, first, count)
 
     def synchronize(self):
         self.engine.synchronize()

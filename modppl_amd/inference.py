@@ -27,6 +27,36 @@ def _dptr(a):
         return a.ctypes.data_as(_DP)
 
 
+def _forecast(L, h, model, horizon, var, obs):
+    """mp_pf_forecast_moments on a filter handle (ParticleSystem.forecast and the sharded classes')"""
+    H = int(horizon)
+    if H < 1:
+        raise capi.ModpplError(capi.MP_ERR_INVALID_ARG, "forecast: horizon must be at least 1")
+    sm = np.empty((H, model.dim_state))
+    sv = np.empty((H, model.dim_state)) if var else None
+    om = np.empty((H, model.dim_obs)) if obs else None
+    ov = np.empty((H, model.dim_obs)) if obs and var else None
+    capi.check(L.mp_pf_forecast_moments(h, H, _dptr(sm), _dptr(sv) if sv is not None else None, _dptr(om) if om is not None else None,
+                                        _dptr(ov) if ov is not None else None))
+    return sm, sv, om, ov
+
+
+def _forecast_paths(L, h, model, horizon, first, count, out=None):
+    """mp_pf_forecast_paths on a filter handle"""
+    H, count = int(horizon), int(count)
+    if H < 1 or count < 0:
+        raise capi.ModpplError(capi.MP_ERR_INVALID_ARG, "forecast_paths: horizon must be at least 1 and count non-negative")
+    if out is None:
+        xs, ys = np.empty((count, H, model.dim_state)), np.empty((count, H, model.dim_obs))
+    else:
+        xs, ys = out
+        for a, w in ((xs, model.dim_state), (ys, model.dim_obs)):
+            if not (isinstance(a, np.ndarray) and a.dtype == _F64 and a.flags.c_contiguous and a.size == count * H * w):
+                raise capi.ModpplError(capi.MP_ERR_INVALID_ARG, "forecast_paths(out=): C-contiguous float64 arrays of count * horizon * width values")
+    capi.check(L.mp_pf_forecast_paths(h, H, int(first), count, _dptr(xs), _dptr(ys)))
+    return xs, ys
+
+
 class ParticleSystem:
     """`ParticleSystem<Args,Data,Ret,F>` over an Unfold model (alias `DynParticles`, dynunfold.rs:20).
 
@@ -198,6 +228,21 @@ class ParticleSystem:
         capi.check(self._L.mp_pf_path_moments(self._h, _dptr(mean), _dptr(v) if var else None,
                                               k.ctypes.data_as(C.POINTER(C.c_uint64)) if distinct else None, C.byref(t)))
         return mean[: t.value], (v[: t.value] if var else None), (k[: t.value] if distinct else None)
+
+    def forecast(self, horizon, var=True, obs=True):
+        """-> (state_mean [H, dim_state], state_var or None, obs_mean [H, dim_obs] or None, obs_var or None): the weighted mean and
+        (population, marginal) variance of where the cloud will be over the next `horizon` steps and of what it will observe — every
+        slot runs the model in Simulate mode from its own state with the Philox counters the next steps would use (dynunfold.rs:66-100
+        with empty constraints), reduced on the device by the trees of `moments()` (mp_pf_forecast_moments; DESIGN.md section 4,
+        "Forecast").  Changes nothing the filter computes afterwards."""
+        return _forecast(self._L, self._h, self.model, horizon, var, obs)
+
+    def forecast_paths(self, horizon, first=0, count=None, out=None):
+        """-> (states [count, H, dim_state], obs [count, H, dim_obs]): the predictive paths of slots first .. first + count - 1
+        (mp_pf_forecast_paths): bit for bit the states the next `horizon` unresampled steps would propose.  `out`: a pair of float64
+        C-contiguous arrays of those sizes to fill instead of fresh ones (pinned ones take the copy at the link's rate)."""
+        count = self.num_particles - int(first) if count is None else int(count)
+        return _forecast_paths(self._L, self._h, self.model, horizon, first, count, out)
 
     def set_timing(self, enabled):
         capi.check(self._L.mp_pf_set_timing(self._h, int(enabled)))

@@ -86,6 +86,9 @@ extern "C" {
     pub fn mp_pf_read_trajectory(h: *mut mp_pf, i: u64, out: *mut f64, t_steps: *mut i32) -> i32;
     pub fn mp_pf_read_trajectories(h: *mut mp_pf, first: u64, count: u64, out: *mut f64, t_steps: *mut i32) -> i32;
     pub fn mp_pf_path_moments(h: *mut mp_pf, mean_out: *mut f64, var_out: *mut f64, distinct_out: *mut u64, t_steps: *mut i32) -> i32;
+    pub fn mp_pf_forecast_paths(h: *mut mp_pf, horizon: i32, first: u64, count: u64, states_out: *mut f64, obs_out: *mut f64) -> i32;
+    pub fn mp_pf_forecast_moments(h: *mut mp_pf, horizon: i32, state_mean_out: *mut f64, state_var_out: *mut f64, obs_mean_out: *mut f64,
+                                  obs_var_out: *mut f64) -> i32;
     pub fn mp_pf_time(h: *mut mp_pf, out: *mut i64) -> i32;
     pub fn mp_pf_run(h: *mut mp_pf, args0: *const f64, obs: *const f64, n_steps: i32, scheme: i32) -> i32;
     pub fn mp_pf_synchronize(h: *mut mp_pf) -> i32;

@@ -103,6 +103,24 @@ impl ParticleSystem {
         check(unsafe { sys::mp_pf_path_moments(self.h, mean.as_mut_ptr(), var.as_mut_ptr(), distinct.as_mut_ptr(), &mut steps) });
         (mean, var, distinct)
     }
+    /// The forecast over the next `horizon` steps (`DynUnfold::update` with `ArgDiff::Extend` and empty constraints, dynunfold.rs:66-100,
+    /// done to every trace): weighted mean and population variance of the state (`[horizon][dim_state]`) and of the observation
+    /// (`[horizon][dim_obs]`), reduced on the device.  -> (state mean, state var, obs mean, obs var)
+    pub fn forecast(&self, horizon: i32) -> (Vec<f64>, Vec<f64>, Vec<f64>, Vec<f64>) {
+        let h = horizon.max(0) as usize;
+        let (d, o) = (self.model.dim_state as usize, self.model.dim_obs as usize);
+        let (mut sm, mut sv, mut om, mut ov) = (vec![0.0; h * d], vec![0.0; h * d], vec![0.0; h * o], vec![0.0; h * o]);
+        check(unsafe { sys::mp_pf_forecast_moments(self.h, horizon, sm.as_mut_ptr(), sv.as_mut_ptr(), om.as_mut_ptr(), ov.as_mut_ptr()) });
+        (sm, sv, om, ov)
+    }
+    /// The predictive paths of slots `first .. first + count`: states `[count][horizon][dim_state]` and observations
+    /// `[count][horizon][dim_obs]`, bit for bit what the next `horizon` unresampled steps would propose.
+    pub fn forecast_paths(&self, horizon: i32, first: usize, count: usize) -> (Vec<f64>, Vec<f64>) {
+        let h = horizon.max(0) as usize;
+        let (mut xs, mut ys) = (vec![0.0; count * h * self.model.dim_state as usize], vec![0.0; count * h * self.model.dim_obs as usize]);
+        check(unsafe { sys::mp_pf_forecast_paths(self.h, horizon, first as u64, count as u64, xs.as_mut_ptr(), ys.as_mut_ptr()) });
+        (xs, ys)
+    }
     /// `log_weights` (pub field of the reference's struct)
     pub fn log_weights(&self) -> Vec<f64> {
         let mut w = vec![0.0; self.num_particles];
