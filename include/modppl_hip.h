@@ -162,6 +162,25 @@ int32_t mp_pf_read_trajectories(mp_pf* h, uint64_t first, uint64_t count, double
  * computes afterwards.  Needs MP_PF_RECORD_HISTORY (else MP_ERR_STATE; also before init_step).  All log-weights -inf:
  * MP_ERR_DEGENERATE.  One shard of a larger world, or a dim_state other than 1, 2, 4, 16: MP_ERR_UNSUPPORTED. */
 int32_t mp_pf_path_moments(mp_pf* h, double* mean_out, double* var_out, uint64_t* distinct_out, int32_t* t_steps);
+/* Weighted QUANTILES of every state component, selected ON THE DEVICE: the median and the credible interval a caller of the reference
+ * gets by sorting what it collects from its public `traces` / `log_weights` fields (particle_filter.rs:13-20), i.e. mp_pf_read_state +
+ * mp_pf_read_log_weights and a host sort.  The definition is in integers only ("Quantiles"): with the weights a_i of
+ * mp_pf_moments, S = 2^min(52, 63 - ceil_log2(n)), W_i = a_i > 0 ? (uint64) trunc(a_i S) : 0 and A = sum W_i, the value for a level q is
+ * the smallest stored value v with sum_{x_ij <= v} W_i >= max(1, ceil(q A)) — the weighted inverted CDF; values are ordered by their
+ * order-preserving 64-bit keys (-0.0 just below +0.0) and the result is one of the stored values with its own bits.  q = 0 is the
+ * smallest value of positive weight, q = 1 the largest; the normalised CDF is within 2 n / S of the one built from the a_i.
+ *   mp_pf_quantiles: out[n_q][dim_state].
+ *   mp_pf_path_quantiles: the same weights over v_ij(t) = the state at time t of slot i's ancestor (the walk of mp_pf_path_moments), for
+ *     every t: out[T][n_q][dim_state], T = mp_pf_time = *t_out; the caller sizes out from mp_pf_time.  Row T - 1 equals mp_pf_quantiles.
+ *     Needs MP_PF_RECORD_HISTORY (else MP_ERR_STATE).
+ * qs[n_q], 1 <= n_q <= 16, each level in [0, 1], in any order, duplicates allowed (else MP_ERR_INVALID_ARG, as for a NULL pointer).
+ * Synchronous, on the handle's stream; both bring the handle to a readable state exactly as mp_pf_moments does and change nothing the
+ * filter computes afterwards (no state, weight, parent, counter, time or history event).  Before init_step: MP_ERR_STATE.  All
+ * log-weights -inf: MP_ERR_DEGENERATE; a NaN log-weight: every output NaN.  One shard of a larger world, a dim_state other than 1, 2,
+ * 4, 16, or T * n_q * dim_state above 2^18 (each such selector owns 2 KiB of device bins; ask for fewer levels per call):
+ * MP_ERR_UNSUPPORTED. */
+int32_t mp_pf_quantiles(mp_pf* h, const double* qs, int32_t n_q, double* out);
+int32_t mp_pf_path_quantiles(mp_pf* h, const double* qs, int32_t n_q, double* out, int32_t* t_out);
 /* The FORECAST: DynUnfold::update with ArgDiff::Extend and EMPTY constraint tries for the new steps (modppl/src/modeling/
  * dynunfold.rs:66-100) runs the kernel from each trace's last state, sample_at's unconstrained arm draws every site and the weight is 0;
  * done to every trace of the filter that is "where will the state be in H steps, and what will I observe".  With H = horizon >= 1 and
@@ -469,6 +488,13 @@ int32_t mp_mh_read_trace(mp_mh* h, double* values, uint32_t* present);
  * are the pairwise tree over chain ids of DESIGN.md section 4.  All arrays [n_sites] (mp_mh_n_sites); the sub-calls' running weights are not
  * summarised.  Hand-written chains (mp_mh_create, mp_mh_create_pointed): MP_ERR_UNSUPPORTED, as for mp_mh_read_trace. */
 int32_t mp_mh_site_moments(mp_mh* h, uint64_t* count_out, double* mean_out, double* var_out);
+/* Per-site QUANTILES over the chains, selected on the device: replaces sorting, per site, what mp_mh_read_trace hands back (what the
+ * reference's tests do with the traces they collect, tests/mh.rs).  For site s, over the count_s chains whose trace holds it, each
+ * weighing 1: out[k][s] = the max(1, ceil(qs[k] count_s))-th smallest value (the inverted CDF of DESIGN.md section 4, "Quantiles"; one of
+ * the stored values, its own bits); count_out[s] = count_s as mp_mh_site_moments gives it.  A site no chain holds: count 0 and NaN (not
+ * an error).  out[n_q][n_sites], count_out[n_sites] (mp_mh_n_sites); qs as for mp_pf_quantiles (else MP_ERR_INVALID_ARG).  Hand-written
+ * chains (mp_mh_create, mp_mh_create_pointed): MP_ERR_UNSUPPORTED, as for mp_mh_read_trace. */
+int32_t mp_mh_site_quantiles(mp_mh* h, const double* qs, int32_t n_q, uint64_t* count_out, double* out);
 
 /* ---- The GFI operations ONE AT A TIME, batched over the chains of a registered generative function ---------------------------
  * `GenFn::update / regenerate / propose / assess` are public in the reference (modppl/src/gfi.rs:57-90) and its tests call them

@@ -33,7 +33,7 @@ MP_MH_PROPOSAL_POINTED_DRIFT = 3
 SYMBOLS = [
     "mp_last_error", "mp_device_count", "mp_pf_create", "mp_pf_init_step", "mp_pf_step", "mp_pf_effective_sample_size",
     "mp_pf_resample", "mp_pf_resample_if_ess_below", "mp_pf_log_marginal_likelihood_estimate", "mp_pf_read_state", "mp_pf_read_log_weights",
-    "mp_pf_read_parents", "mp_pf_moments", "mp_pf_read_trajectory", "mp_pf_read_trajectories", "mp_pf_path_moments", "mp_pf_forecast_paths", "mp_pf_forecast_moments", "mp_pf_time", "mp_pf_run", "mp_pf_synchronize", "mp_pf_destroy",
+    "mp_pf_read_parents", "mp_pf_moments", "mp_pf_read_trajectory", "mp_pf_read_trajectories", "mp_pf_path_moments", "mp_pf_quantiles", "mp_pf_path_quantiles", "mp_pf_forecast_paths", "mp_pf_forecast_moments", "mp_pf_time", "mp_pf_run", "mp_pf_synchronize", "mp_pf_destroy",
     "mp_pf_set_timing", "mp_pf_get_timing", "mp_pf_region_begin", "mp_pf_region_end", "mp_pf_last_propagate_form", "mp_unfold_simulate", "mp_importance_resampling", "mp_importance_sampling",
     "mp_pf_shard_bind_tiles", "mp_pf_shard_tiles_packed", "mp_pf_shard_route_fixed", "mp_pf_shard_resolve_fixed", "mp_pf_shard_commit_fixed", "mp_pf_shard_query_packed",
     "mp_pf_shard_owned_count", "mp_pf_shard_owned_expand", "mp_pf_shard_owned_commit", "mp_pf_shard_owned_count_expand",
@@ -41,7 +41,7 @@ SYMBOLS = [
     "mp_rccl_available", "mp_rccl_unique_id", "mp_rccl_comm_create", "mp_rccl_comm_destroy", "mp_pf_stream_copy",
     "mp_pf_shard_tiles", "mp_pf_shard_route", "mp_pf_shard_resolve", "mp_pf_shard_scatter", "mp_pf_shard_query",
     "mp_mh_create", "mp_mh_create_pointed", "mp_mh_step", "mp_regen_mh_step", "mp_mh_read_state", "mp_mh_read_logjp", "mp_mh_read_observations", "mp_mh_iterations", "mp_mh_destroy",
-    "mp_mh_create_fn", "mp_mh_n_sites", "mp_mh_read_trace", "mp_mh_site_moments", "mp_fn_update", "mp_fn_regenerate", "mp_fn_assess", "mp_fn_propose",
+    "mp_mh_create_fn", "mp_mh_n_sites", "mp_mh_read_trace", "mp_mh_site_moments", "mp_mh_site_quantiles", "mp_fn_update", "mp_fn_regenerate", "mp_fn_assess", "mp_fn_propose",
     "mp_fn_generate", "mp_fn_simulate", "mp_fn_generate_create", "mp_fn_simulate_create", "mp_fn_importance_sampling", "mp_fn_importance_resampling",
     # include/modppl_hip_probe.h
     "mp_probe_math", "mp_probe_normal_sample", "mp_probe_u01", "mp_probe_mfma_f64", "mp_probe_mvnormal", "mp_probe_dist",
@@ -152,6 +152,8 @@ def _load_so(so):
     L.mp_pf_read_trajectory.argtypes = [p, u64, dp, C.POINTER(i32)]
     L.mp_pf_read_trajectories.argtypes = [p, u64, u64, dp, C.POINTER(i32)]
     L.mp_pf_path_moments.argtypes = [p, dp, dp, C.POINTER(u64), C.POINTER(i32)]
+    L.mp_pf_quantiles.argtypes = [p, dp, i32, dp]
+    L.mp_pf_path_quantiles.argtypes = [p, dp, i32, dp, C.POINTER(i32)]
     L.mp_pf_forecast_paths.argtypes = [p, i32, u64, u64, dp, dp]
     L.mp_pf_forecast_moments.argtypes = [p, i32, dp, dp, dp, dp]
     L.mp_pf_time.argtypes = [p, C.POINTER(i64)]
@@ -204,6 +206,7 @@ def _load_so(so):
     L.mp_mh_n_sites.argtypes = [p, C.POINTER(i32)]
     L.mp_mh_read_trace.argtypes = [p, dp, C.POINTER(u32)]
     L.mp_mh_site_moments.argtypes = [p, C.POINTER(u64), dp, dp]
+    L.mp_mh_site_quantiles.argtypes = [p, dp, i32, C.POINTER(u64), dp]
     L.mp_fn_update.argtypes = [p, i32, u32, C.POINTER(i32), dp, i32, dp, C.POINTER(u32), dp, dp, C.POINTER(u32)]
     L.mp_fn_regenerate.argtypes = [p, i32, u32, C.POINTER(i32), i32, dp]
     L.mp_fn_assess.argtypes = [p, i32, dp, i32, u32, C.POINTER(i32), dp, i32, dp, C.POINTER(u32), dp]

@@ -108,6 +108,24 @@ public:
         check(mp_pf_path_moments(h_, m.mean.data(), var ? m.var.data() : nullptr, distinct ? m.distinct.data() : nullptr, &steps));
         return m;
     }
+    // weighted quantiles of every state component at the levels qs (1 to 16, each in [0, 1]), [qs.size()][dim_state] row-major, selected
+    // on the device (mp_pf_quantiles): sorting states() under log_weights() on the host, without moving the particles.  The weighted
+    // inverted CDF over integer weights: every value is one of the stored states
+    std::vector<double> quantiles(const std::vector<double>& qs) {
+        std::vector<double> out(qs.size() * (size_t)model_.dim_state);
+        check(mp_pf_quantiles(h_, qs.data(), (int32_t)qs.size(), out.data()));
+        return out;
+    }
+    // ... and of the state at every time step over the recorded ancestry, [t][qs.size()][dim_state] row-major (mp_pf_path_quantiles; a
+    // filter created with MP_PF_RECORD_HISTORY): the bands of a fan chart without moving n * t * dim_state doubles
+    std::vector<double> path_quantiles(const std::vector<double>& qs) {
+        int64_t t = 0;
+        check(mp_pf_time(h_, &t));
+        std::vector<double> out((size_t)t * qs.size() * (size_t)model_.dim_state);
+        int32_t steps = 0;
+        check(mp_pf_path_quantiles(h_, qs.data(), (int32_t)qs.size(), out.data(), &steps));
+        return out;
+    }
     // the forecast over the next `horizon` steps (mp_pf_forecast_moments / _paths; dynunfold.rs:66-100 with empty constraints): every
     // slot runs the model in Simulate mode from its own state with the counters the next steps would use.  Moments: weighted mean and
     // population variance of the state [H][dim_state] and of the observation [H][dim_obs], reduced on the device; empty where not asked for
@@ -268,6 +286,14 @@ public:
         SiteMoments m{std::vector<uint64_t>((size_t)ns_), std::vector<double>((size_t)ns_), std::vector<double>(var ? (size_t)ns_ : 0)};
         check(mp_mh_site_moments(h_, m.count.data(), m.mean.data(), var ? m.var.data() : nullptr));
         return m;
+    }
+    // per site, over the chains whose trace holds it: the max(1, ceil(q count))-th smallest value for every level of qs (1 to 16, each in
+    // [0, 1]), values [qs.size()][n_sites] row-major, selected on the device (mp_mh_site_quantiles); a site no chain holds: count 0, NaN
+    struct SiteQuantiles { std::vector<uint64_t> count; std::vector<double> values; };
+    SiteQuantiles site_quantiles(const std::vector<double>& qs) {
+        SiteQuantiles q{std::vector<uint64_t>((size_t)ns_), std::vector<double>(qs.size() * (size_t)ns_)};
+        check(mp_mh_site_quantiles(h_, qs.data(), (int32_t)qs.size(), q.count.data(), q.values.data()));
+        return q;
     }
     // ---- GenFn::update / regenerate / assess / propose one at a time, every chain per call (gfi.rs:57-90; mp_fn_* of the C ABI) ----
     // A per-chain table of choices: values[chain][site], present[chain][words()] — what propose() and update()'s discard return.

@@ -400,11 +400,16 @@ struct mp_mh {           // (every device pointer is a holder, mp_hip_own.h; the
     // mp_mh_site_moments (mp_moments.h), allocated on first use: partials of one pass ([columns][workgroups], two levels), the closed trees
     mp_dev<double> mom_buf[2];
     mp_dev<double> mom_res;          // {sum, count}[n_sites], mean[n_sites], centred sum of squares[n_sites]
+    // mp_mh_site_quantiles (mp_quantiles.h), allocated on first use: the bins, {prefix, target, total} and the value of each (quantile, site)
+    mp_dev<u64> q_bins, q_st;        // [16 n_sites][256], [3][16 n_sites]
+    mp_dev<double> q_out;            // [16 n_sites]
     mp_dev<double> d_data;           // models with declared data sites (mp_genfn.h): [2][n_obs] = the covariates (params), the observed values
 };
 #include "mp_mh_fn.h"
 #define MP_MOMENTS_MH
 #include "mp_moments.h"   // mp_mh_site_moments: the tree reduction and its kernels (after every existing kernel)
+#define MP_QUANTILES_MH
+#include "mp_quantiles.h" // mp_mh_site_quantiles: the integer radix select and its kernels
 
 // acceptance count (and, for registered functions, the count of chains that reached a state the reference panics on)
 static int32_t mh_finish(mp_mh* h, uint64_t* accepted) {
@@ -744,6 +749,40 @@ int32_t mp_mh_site_moments(mp_mh* h, uint64_t* count_out, double* mean_out, doub
         mean_out[s] = var_out ? r[2 * ns + s] : r[2 * s] / cnt;
         if (var_out) var_out[s] = r[3 * ns + s] / cnt;
     }
+    return MP_OK;
+}
+
+// Per-site quantiles over the chains whose trace holds the site, selected on the device: replaces sorting, per site, what a caller of the
+// reference collects from its public traces (tests/mh.rs; here mp_mh_read_trace and a host sort).  Every holding chain weighs 1:
+// Q(q) is the max(1, ceil(q count_s))-th smallest value.  Definition: mp_quantiles.h, DESIGN.md section 4, "Quantiles".
+int32_t mp_mh_site_quantiles(mp_mh* h, const double* qs, int32_t n_q, uint64_t* count_out, double* out) {
+    if (!h || !qs || !count_out || !out) return mp_set_error(MP_ERR_INVALID_ARG, "null argument");
+    q_spec spec;
+    if (!q_make_spec(qs, n_q, spec)) return mp_set_error(MP_ERR_INVALID_ARG, "mp_mh_site_quantiles: n_q outside [1, 16], or a level that is NaN or outside [0, 1]");
+    if (!h->fn) return mp_set_error(MP_ERR_UNSUPPORTED, "chains of a registered generative function only (mp_mh_create_fn)");
+    HIPCK(hipSetDevice(h->device));
+    const int ns = h->fn->ns();
+    const size_t cap = (size_t)Q_MAX_Q * ns, nsel = (size_t)n_q * ns;
+    if (!h->q_out) {
+        HIPCK(mp_hipMalloc(h->q_bins, cap * Q_BINS));
+        HIPCK(mp_hipMalloc(h->q_st, 3 * cap));
+        HIPCK(mp_hipMalloc(h->q_out, cap));
+    }
+    const q_bufs b{h->q_bins.get(), h->q_st.get(), h->q_st.get() + cap, h->q_st.get() + 2 * cap, h->q_out.get()};
+    const unsigned nb = (unsigned)((h->n + (u64)Q_THREADS * Q_ROWS - 1) / ((u64)Q_THREADS * Q_ROWS));
+    hipError_t e = q_select(h->stream, b, nsel, n_q, ns, spec, [&](int pass, int nq, const q_bufs& bb) {
+        hipLaunchKernelGGL(k_q_hist_site, dim3(nb, (unsigned)ns), dim3(Q_THREADS), 0, h->stream, h->n, (const double*)h->fvals, (const uint32_t*)h->fpresent, pass, nq, bb);
+    });
+    // (the vectors stay alive until the stream is idle)
+    std::vector<double> r(nsel);
+    std::vector<u64> tot((size_t)ns);
+    if (e == hipSuccess) e = hipMemcpyAsync(r.data(), b.out, sizeof(double) * nsel, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tot.data(), b.tot, sizeof(u64) * (size_t)ns, hipMemcpyDeviceToHost, h->stream);   // (quantile 0's totals: count_s)
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return mp_set_error(MP_ERR_HIP, std::string("mp_mh_site_quantiles: ") + hipGetErrorString(e));
+    for (int s = 0; s < ns; ++s) count_out[s] = tot[(size_t)s];
+    memcpy(out, r.data(), sizeof(double) * nsel);
     return MP_OK;
 }
 

@@ -73,6 +73,8 @@ int32_t mp_set_error(int32_t code, const std::string& msg) { return mp_fail(code
 #define MP_MOMENTS_PF
 #include "mp_moments.h"   // mp_pf_moments: the tree reduction and its kernels (after every existing kernel)
 #include "mp_forecast.h"  // mp_pf_forecast_paths / _moments: Simulate mode from the cloud, through the same trees
+#define MP_QUANTILES_PF
+#include "mp_quantiles.h" // mp_pf_quantiles / _path_quantiles: the integer radix select and its kernels
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -456,6 +458,14 @@ struct mp_pf {
     size_t fc_cap_h = 0;                   // the H they hold
     mp_dev<double> fc_paths[2];            // states, observations
     size_t fc_paths_cap[2] = {0, 0};       // (doubles)
+    // mp_pf_quantiles / mp_pf_path_quantiles (mp_quantiles.h), allocated on first use and grown with the selectors (n_q * dim_state, per
+    // time step for the paths): the integer weights, the bins, {prefix, target, total} per selector, {m, Q[selectors]} and their host copy
+    mp_dev<u64> q_W;                       // [n]
+    mp_dev<u64> q_bins, q_st;              // [cap][256], [3][cap]
+    mp_dev<double> q_out;                  // [1 + cap]
+    mp_dev<double> q_max[2];               // partials of the max pass
+    mp_pinned<double> q_host;
+    size_t q_cap = 0;                      // the selectors they hold
     // host-side filter state
     long long t = 0;  // Unfold steps taken (trace.args.0)
     uint32_t resample_count = 0;
@@ -862,6 +872,77 @@ static void path_close(hipStream_t stream, double* const buf[2], u64 nb, u64 col
         double* const part[2] = {buf[0] + c0 * nb, buf[1] + c0 * nn};
         mom_close<mom_add>(stream, part, nb, (unsigned)std::min<u64>(65535, cols - c0), dst + c0);
     }
+}
+
+// mp_pf_quantiles / mp_pf_path_quantiles: the checks both share, the handle brought to a readable state (as mp_pf_moments does), room
+// for nsel_per_t * max(T, 1) selectors, then m = max lw -> q_out[0] and the integer weights -> q_W, enqueued on the handle's stream
+static int32_t quantiles_begin(mp_pf* h, const char* who, const double* qs, int32_t n_q, bool path, q_spec& spec, q_bufs& b, size_t& nsel) {
+    if (!q_make_spec(qs, n_q, spec)) return mp_fail(MP_ERR_INVALID_ARG, std::string(who) + ": n_q outside [1, 16], or a level that is NaN or outside [0, 1]");
+    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, std::string(who) + ": one shard of a larger world (n_global != n_particles); the quantiles of a sharded job need an all-reduce of the max and of the bins");
+    if (path && !(h->flags & MP_PF_RECORD_HISTORY)) return mp_fail(MP_ERR_STATE, std::string(who) + " needs a filter created with MP_PF_RECORD_HISTORY");
+    if (!h->initialised) return mp_fail(MP_ERR_STATE, std::string(who) + " before init_step");
+    const int d = h->ops->dim_state;
+    if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, std::string(who) + ": no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
+    HIPCK(hipSetDevice(h->device));
+    MPCK(materialize(h));
+    MPCK(ensure_x(h));
+    MPCK(ensure_lazy(h));
+    if (path) {
+        size_t n_step_events = 0;
+        for (const auto& e : h->hist) n_step_events += e.kind == 0;
+        if (n_step_events != (size_t)h->t) return mp_fail(MP_ERR_STATE, std::string(who) + ": the recorded history does not hold one state per step");
+    }
+    nsel = (size_t)n_q * d * (path ? (size_t)h->t : 1);
+    // every selector owns 2 KiB of bins, refilled on each pass: a call is held to Q_MAX_SEL of them (0.5 GiB) rather than left to hipMalloc
+    if (nsel > (size_t)Q_MAX_SEL) return mp_fail(MP_ERR_UNSUPPORTED, std::string(who) + ": time steps * n_q * dim_state exceeds " + std::to_string(Q_MAX_SEL) + " selectors; ask for fewer levels per call");
+    const u64 nb_max = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);
+    if (!h->q_W) {
+        HIPCK(mp_hipMalloc(h->q_max[0], nb_max));
+        HIPCK(mp_hipMalloc(h->q_max[1], (nb_max + MOM_TREE_RUN - 1) / MOM_TREE_RUN));
+        HIPCK(mp_hipMalloc(h->q_W, h->n));
+    }
+    if (h->q_cap < nsel) {
+        const size_t cap = std::min<size_t>((size_t)Q_MAX_SEL, std::max<size_t>((size_t)Q_MAX_Q * MOM_MAX_DIM, 2 * nsel));
+        h->q_cap = 0;
+        HIPCK(mp_hipMalloc(h->q_bins, cap * Q_BINS));
+        HIPCK(mp_hipMalloc(h->q_st, 3 * cap));
+        HIPCK(mp_hipMalloc(h->q_out, 1 + cap));
+        HIPCK(mp_hipHostMalloc(h->q_host, 1 + cap));
+        h->q_cap = cap;
+    }
+    b = q_bufs{h->q_bins.get(), h->q_st.get(), h->q_st.get() + h->q_cap, h->q_st.get() + 2 * h->q_cap, h->q_out.get() + 1};
+    if (nsel == 0) return MP_OK;   // (a history filter at time 0)
+    double* const buf[2] = {h->q_max[0].get(), h->q_max[1].get()};
+    hipLaunchKernelGGL(k_mom_max0, dim3((unsigned)nb_max), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->logw, buf[0]);
+    mom_close<mom_max>(h->stream, buf, nb_max, 1, h->q_out.get());
+    hipLaunchKernelGGL(k_q_weights, dim3((unsigned)((h->n + Q_THREADS - 1) / Q_THREADS)), dim3(Q_THREADS), 0, h->stream, h->n, (const double*)h->logw,
+                       (const double*)h->q_out.get(), q_scale(h->n), h->q_W.get());
+    return check_launch("mp_pf quantile weights");
+}
+// ... and the end: {m, Q[nsel]} to the host, the one wait, the statuses m decides
+static int32_t quantiles_end(mp_pf* h, hipError_t e1, size_t nsel, double* out) {
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(h->q_host, h->q_out, sizeof(double) * (1 + nsel), hipMemcpyDeviceToHost, h->stream);
+    if (e1 != hipSuccess) { (void)hipStreamSynchronize(h->stream); return mp_fail(MP_ERR_HIP, std::string("quantiles: ") + hipGetErrorString(e1)); }
+    HIPCK(stream_wait(h->stream));
+    const double* r = h->q_host;
+    if (r[0] == -MP_INF) return mp_fail_degenerate();
+    // (a NaN max: every weight is 0, every selector was clamped and holds NaN already)
+    memcpy(out, r + 1, sizeof(double) * nsel);
+    return MP_OK;
+}
+template <int D>
+static void launch_quantiles_hist(mp_pf* h, int pass, int nq, const q_bufs& b) {
+    const unsigned nb = (unsigned)((h->n + (u64)Q_THREADS * Q_ROWS - 1) / ((u64)Q_THREADS * Q_ROWS));
+    constexpr int QC = Q_SEL_CHUNK / D;
+    hipLaunchKernelGGL((k_q_hist_pf<D>), dim3(nb, (unsigned)((nq + QC - 1) / QC)), dim3(Q_THREADS), 0, h->stream, h->n, (const double*)h->x[h->cur],
+                       (const u64*)h->q_W.get(), pass, nq, b);
+}
+template <int D>
+static void launch_path_quantiles_hist(mp_pf* h, int pass, int nq, int Q, const q_bufs& b) {
+    constexpr int R = mom_run<D>::R, QC = Q_SEL_CHUNK / D;
+    const unsigned nb = (unsigned)((h->n + (u64)Q_THREADS * R - 1) / ((u64)Q_THREADS * R));
+    hipLaunchKernelGGL((k_q_hist_path<D>), dim3(nb, (unsigned)((nq + QC - 1) / QC)), dim3(Q_THREADS), 0, h->stream, h->n, (int)h->hist.size(), (int)h->t,
+                       (const mp_hist_event*)h->d_hist_events, (const u64*)h->q_W.get(), pass, nq, Q, b);
 }
 
 extern "C" {
@@ -2046,6 +2127,55 @@ int32_t mp_pf_path_moments(mp_pf* h, double* mean_out, double* var_out, uint64_t
         for (size_t c = 0; c < TD; ++c) var_out[c] = r[2 + 2 * TD + c] / A;
     if (distinct_out) memcpy(distinct_out, r + 2 + 3 * TD, sizeof(uint64_t) * (size_t)T);
     return MP_OK;
+}
+
+// Weighted quantiles of every state component of the cloud, selected on the device: replaces sorting what a caller of the reference
+// collects from its public `traces` / `log_weights` fields (particle_filter.rs:13-20) — here mp_pf_read_state + mp_pf_read_log_weights
+// and a host sort.  Definition (integers only: the weighted inverted CDF over order-preserving keys): mp_quantiles.h, DESIGN.md
+// section 4, "Quantiles".  As in mp_pf_moments every launch is enqueued before the one wait, and m is looked at once, at the end.
+int32_t mp_pf_quantiles(mp_pf* h, const double* qs, int32_t n_q, double* out) {
+    if (!h || !qs || !out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
+    q_spec spec;
+    q_bufs b;
+    size_t nsel = 0;
+    MPCK(quantiles_begin(h, "mp_pf_quantiles", qs, n_q, false, spec, b, nsel));
+    const int d = h->ops->dim_state;
+    const hipError_t e1 = q_select(h->stream, b, nsel, n_q, d, spec, [&](int pass, int nq, const q_bufs& bb) {
+        switch (d) {
+        case 1: launch_quantiles_hist<1>(h, pass, nq, bb); break;
+        case 2: launch_quantiles_hist<2>(h, pass, nq, bb); break;
+        case 4: launch_quantiles_hist<4>(h, pass, nq, bb); break;
+        default: launch_quantiles_hist<16>(h, pass, nq, bb); break;
+        }
+    });
+    return quantiles_end(h, e1, nsel, out);
+}
+
+// Weighted quantiles of the state at EVERY time step over the recorded ancestry (the bands of a fan chart), selected on the device:
+// replaces walking `traces[i].retv` of every particle (particle_filter.rs:13; tests/smc.rs:67) and sorting per step on the host — here
+// mp_pf_read_trajectories, n * T * d doubles over the link.  The weights of mp_pf_quantiles over v_ij(t) = x_t[anc_i(t)]; the walk of
+// mp_pf_path_moments, once per pass.  Definition: mp_quantiles.h, DESIGN.md section 4, "Quantiles".
+int32_t mp_pf_path_quantiles(mp_pf* h, const double* qs, int32_t n_q, double* out, int32_t* t_out) {
+    if (!h || !qs || !out || !t_out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
+    q_spec spec;
+    q_bufs b;
+    size_t nsel = 0;
+    MPCK(quantiles_begin(h, "mp_pf_path_quantiles", qs, n_q, true, spec, b, nsel));
+    *t_out = (int32_t)h->t;
+    if (h->t == 0) return MP_OK;
+    const int d = h->ops->dim_state;
+    std::vector<mp_hist_event> ev;   // (stays alive until the stream is idle: quantiles_end waits on every path)
+    const int32_t up = upload_hist_events(h, ev);
+    if (up != MP_OK) { (void)hipStreamSynchronize(h->stream); return up; }   // (a copy out of ev may be in flight: wait, then the status as it came)
+    const hipError_t e1 = q_select(h->stream, b, nsel, n_q, d, spec, [&](int pass, int nq, const q_bufs& bb) {
+        switch (d) {
+        case 1: launch_path_quantiles_hist<1>(h, pass, nq, n_q, bb); break;
+        case 2: launch_path_quantiles_hist<2>(h, pass, nq, n_q, bb); break;
+        case 4: launch_path_quantiles_hist<4>(h, pass, nq, n_q, bb); break;
+        default: launch_path_quantiles_hist<16>(h, pass, nq, n_q, bb); break;
+        }
+    });
+    return quantiles_end(h, e1, nsel, out);
 }
 
 // The forecast (mp_forecast.h; DESIGN.md section 4, "Forecast"): DynUnfold::update with ArgDiff::Extend and EMPTY constraints for the new

@@ -229,6 +229,26 @@ class ParticleSystem:
                                               k.ctypes.data_as(C.POINTER(C.c_uint64)) if distinct else None, C.byref(t)))
         return mean[: t.value], (v[: t.value] if var else None), (k[: t.value] if distinct else None)
 
+    def quantiles(self, qs):
+        """-> [len(qs), dim_state]: the weighted quantiles of every state component under the current log-weights, selected on the device
+        (mp_pf_quantiles) — what `states()` + `log_weights` and a host sort give, without moving the particles.  The weighted inverted
+        CDF over integer weights ("Quantiles"): each value is one of the stored states, the same bits on every
+        call.  1 to 16 levels in [0, 1], in any order."""
+        q = _levels(qs)
+        out = np.empty((q.size, self.model.dim_state))
+        capi.check(self._L.mp_pf_quantiles(self._h, _dptr(q), q.size, _dptr(out)))
+        return out
+
+    def path_quantiles(self, qs):
+        """-> [t, len(qs), dim_state]: the quantiles of `quantiles()` of the state at every time step over the recorded ancestry — the
+        bands of a fan chart, the weighted quantiles of `trajectories()` under the current log-weights — selected on the device by one
+        walk of the ancestry per pass (mp_pf_path_quantiles; needs flags=MP_PF_RECORD_HISTORY).  The last row equals `quantiles(qs)`."""
+        q = _levels(qs)
+        out = np.empty((max(self.time, 1), q.size, self.model.dim_state))
+        t = C.c_int32()
+        capi.check(self._L.mp_pf_path_quantiles(self._h, _dptr(q), q.size, _dptr(out), C.byref(t)))
+        return out[: t.value]
+
     def forecast(self, horizon, var=True, obs=True):
         """-> (state_mean [H, dim_state], state_var or None, obs_mean [H, dim_obs] or None, obs_var or None): the weighted mean and
         (population, marginal) variance of where the cloud will be over the next `horizon` steps and of what it will observe — every
@@ -411,6 +431,10 @@ class HierarchicalChains:
         (MP_ERR_UNSUPPORTED, as for mp_mh_read_trace)"""
         return _site_moments(self._L, self._h, var)
 
+    def site_quantiles(self, qs):
+        """registered-function chains only (functor=True): FunctionChains.site_quantiles (MP_ERR_UNSUPPORTED otherwise)"""
+        return _site_quantiles(self._L, self._h, qs)
+
     def states(self):
         """[num_chains, 4] = is_linear, a, b, c  (read_coeffs of hierarchical.rs:5-16)."""
         if self._fn is not None:
@@ -455,6 +479,21 @@ class HierarchicalChains:
             self.close()
         except Exception:
             pass
+
+
+def _levels(qs):
+    """the quantile levels of a call as the C ABI takes them (it checks their count and range)"""
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(qs, dtype=np.float64)).ravel())
+
+
+def _site_quantiles(L, h, qs):
+    ns = C.c_int32()
+    capi.check(L.mp_mh_n_sites(h, C.byref(ns)))   # (hand-written chains stop here: MP_ERR_UNSUPPORTED)
+    q = _levels(qs)
+    count = np.empty(ns.value, dtype=np.uint64)
+    out = np.empty((q.size, ns.value))
+    capi.check(L.mp_mh_site_quantiles(h, _dptr(q), q.size, count.ctypes.data_as(C.POINTER(C.c_uint64)), _dptr(out)))
+    return count, out
 
 
 def _site_moments(L, h, var):
@@ -602,6 +641,12 @@ class FunctionChains:
         on the device (mp_mh_site_moments) — what trace() and a host-side mean over chains give.  A site no chain holds: count 0, NaN."""
         return _site_moments(self._L, self._h, var)
 
+    def site_quantiles(self, qs):
+        """-> (count [num_sites] uint64, [len(qs), num_sites]): per site, over the chains whose trace holds it, the
+        max(1, ceil(q count))-th smallest value, selected on the device (mp_mh_site_quantiles) — what trace() and a host sort per site
+        give.  A site no chain holds: count 0, NaN.  1 to 16 levels in [0, 1]."""
+        return _site_quantiles(self._L, self._h, qs)
+
     # ---- the GFI operations one at a time (modppl/src/gfi.rs:57-90), every chain per call ------------------------------------
     # constraints: {site: value} shared by all chains, or a (values [num_chains, num_sites], present [num_chains]) pair per chain
     # (what propose() and update()'s discard return).  rng_step = 0: the next MH iteration's Philox step, which the call consumes.
@@ -715,6 +760,12 @@ class PointedChains:
         if self._fn is not None:
             return self._fn.site_moments(var)
         return _site_moments(self._L, self._h, var)
+
+    def site_quantiles(self, qs):
+        """registered-function chains only (functor=True); MP_ERR_UNSUPPORTED otherwise"""
+        if self._fn is not None:
+            return self._fn.site_quantiles(qs)
+        return _site_quantiles(self._L, self._h, qs)
 
     def states(self):
         """[num_chains, 2] = latent."""

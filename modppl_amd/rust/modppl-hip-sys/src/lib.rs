@@ -86,6 +86,8 @@ extern "C" {
     pub fn mp_pf_read_trajectory(h: *mut mp_pf, i: u64, out: *mut f64, t_steps: *mut i32) -> i32;
     pub fn mp_pf_read_trajectories(h: *mut mp_pf, first: u64, count: u64, out: *mut f64, t_steps: *mut i32) -> i32;
     pub fn mp_pf_path_moments(h: *mut mp_pf, mean_out: *mut f64, var_out: *mut f64, distinct_out: *mut u64, t_steps: *mut i32) -> i32;
+    pub fn mp_pf_quantiles(h: *mut mp_pf, qs: *const f64, n_q: i32, out: *mut f64) -> i32;
+    pub fn mp_pf_path_quantiles(h: *mut mp_pf, qs: *const f64, n_q: i32, out: *mut f64, t_out: *mut i32) -> i32;
     pub fn mp_pf_forecast_paths(h: *mut mp_pf, horizon: i32, first: u64, count: u64, states_out: *mut f64, obs_out: *mut f64) -> i32;
     pub fn mp_pf_forecast_moments(h: *mut mp_pf, horizon: i32, state_mean_out: *mut f64, state_var_out: *mut f64, obs_mean_out: *mut f64,
                                   obs_var_out: *mut f64) -> i32;
@@ -157,6 +159,7 @@ extern "C" {
     pub fn mp_mh_n_sites(h: *mut mp_mh, out: *mut i32) -> i32;
     pub fn mp_mh_read_trace(h: *mut mp_mh, values: *mut f64, present: *mut u32) -> i32;
     pub fn mp_mh_site_moments(h: *mut mp_mh, count_out: *mut u64, mean_out: *mut f64, var_out: *mut f64) -> i32;
+    pub fn mp_mh_site_quantiles(h: *mut mp_mh, qs: *const f64, n_q: i32, count_out: *mut u64, out: *mut f64) -> i32;
     pub fn mp_fn_update(h: *mut mp_mh, argdiff: i32, rng_step: u32, sites: *const i32, values: *const f64, n_constraints: i32,
                         chain_values: *const f64, chain_present: *const u32, weights_out: *mut f64, discard_values_out: *mut f64,
                         discard_present_out: *mut u32) -> i32;

@@ -103,6 +103,24 @@ impl ParticleSystem {
         check(unsafe { sys::mp_pf_path_moments(self.h, mean.as_mut_ptr(), var.as_mut_ptr(), distinct.as_mut_ptr(), &mut steps) });
         (mean, var, distinct)
     }
+    /// Weighted quantiles of every state component at the levels `qs` (1 to 16, each in `[0, 1]`), `[qs.len()][dim_state]` row-major,
+    /// selected on the device: what sorting `states()` under `log_weights()` gives, without moving the particles.  The weighted inverted
+    /// CDF over integer weights: every value is one of the stored states.
+    pub fn quantiles(&self, qs: &[f64]) -> Vec<f64> {
+        let mut out = vec![0.0; qs.len() * self.model.dim_state as usize];
+        check(unsafe { sys::mp_pf_quantiles(self.h, qs.as_ptr(), qs.len() as i32, out.as_mut_ptr()) });
+        out
+    }
+    /// ... and of the state at every time step over the recorded ancestry, `[t][qs.len()][dim_state]` row-major (a filter created with
+    /// `MP_PF_RECORD_HISTORY`): the bands of a fan chart without moving `n * t * dim_state` doubles.
+    pub fn path_quantiles(&self, qs: &[f64]) -> Vec<f64> {
+        let mut t = 0i64;
+        check(unsafe { sys::mp_pf_time(self.h, &mut t) });
+        let mut out = vec![0.0; t as usize * qs.len() * self.model.dim_state as usize];
+        let mut steps = 0i32;
+        check(unsafe { sys::mp_pf_path_quantiles(self.h, qs.as_ptr(), qs.len() as i32, out.as_mut_ptr(), &mut steps) });
+        out
+    }
     /// The forecast over the next `horizon` steps (`DynUnfold::update` with `ArgDiff::Extend` and empty constraints, dynunfold.rs:66-100,
     /// done to every trace): weighted mean and population variance of the state (`[horizon][dim_state]`) and of the observation
     /// (`[horizon][dim_obs]`), reduced on the device.  -> (state mean, state var, obs mean, obs var)
@@ -331,6 +349,13 @@ impl FunctionChains {
         let (mut c, mut m, mut v) = (vec![0u64; self.n_sites], vec![0.0; self.n_sites], vec![0.0; self.n_sites]);
         check(unsafe { sys::mp_mh_site_moments(self.h, c.as_mut_ptr(), m.as_mut_ptr(), v.as_mut_ptr()) });
         (c, m, v)
+    }
+    /// Per site, over the chains whose trace holds it: `(count, values [qs.len()][n_sites])`, the `max(1, ceil(q count))`-th smallest
+    /// value for every level of `qs` (1 to 16, each in `[0, 1]`), selected on the device; a site no chain holds has count 0 and NaN.
+    pub fn site_quantiles(&self, qs: &[f64]) -> (Vec<u64>, Vec<f64>) {
+        let (mut c, mut v) = (vec![0u64; self.n_sites], vec![0.0; qs.len() * self.n_sites]);
+        check(unsafe { sys::mp_mh_site_quantiles(self.h, qs.as_ptr(), qs.len() as i32, c.as_mut_ptr(), v.as_mut_ptr()) });
+        (c, v)
     }
     // ---- `GenFn::update / regenerate / assess / propose` (gfi.rs:57-90) one at a time, every chain per call ----
     /// `(new_trace, discard, weight) = model.update(trace, args, diff, constraints)` with per-chain constraints
