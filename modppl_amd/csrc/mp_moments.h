@@ -28,6 +28,9 @@
 // pairs one at a time — one accumulator tree per pair, never 136 live accumulators; see DESIGN.md §5 for the VGPR / scratch figures.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <type_traits>
+#include "mp_hip_own.h"
 #include "mp_math.h"
 
 #define MOM_THREADS 256
@@ -365,16 +368,77 @@ __global__ __launch_bounds__(MOM_THREADS) void k_mom_site2(unsigned long long n,
 
 #endif   // MP_MOMENTS_MH
 
-// ---- host side: close the trees of `cols` columns of `nb` partials each ([cols][nb] in buf[0]) into dst[cols] -----------------------------
-// buf[0] holds cols * nb doubles, buf[1] cols * ceil(nb / 1024).  At least one launch: a single partial goes through the tree as v + 0.
+// ---- host side -------------------------------------------------------------------------------------------------------------------------
+static inline bool mom_width_ok(int d) { return d == 1 || d == 2 || d == 4 || d == MOM_MAX_DIM; }   // the compiled models' widths
+// f(std::integral_constant<int, D>) for D = d: the one place that turns a run-time width into a kernel's template argument
+template <class F>
+static inline void mom_for_width(int d, F&& f) {
+    switch (d) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, MOM_MAX_DIM>{}); break;
+    }
+}
+
+// The grids of a reduction over n slots of width d: nb workgroups for the level-0 passes (R = mom_run<D>::R slots per lane, the kernels'
+// own constant), nb_max <= nb for the max pass, nn partials per column after the first k_mom_tree level.
+// k_mom_max0's slots per lane.  A known leftover: the kernel's own `constexpr int R = 8` is a literal in device text, which stays as it
+// is, so this copy is tied to it by this comment only (unlike the moment passes' R, which comes from mom_run<D>::R below).
+constexpr int MOM_MAX0_R = 8;
+static inline unsigned long long mom_blocks(unsigned long long n, int R) {
+    return (n + (unsigned long long)MOM_THREADS * R - 1) / ((unsigned long long)MOM_THREADS * R);
+}
+struct mom_grids { unsigned long long nb, nb_max, nn; };
+static inline mom_grids mom_plan(unsigned long long n, int d) {
+    mom_grids g{};
+    mom_for_width(d, [&](auto D) {
+        constexpr int R = mom_run<decltype(D)::value>::R;
+        static_assert(R <= MOM_MAX0_R, "the max pass must not need more partials than a moment pass: one scratch holds both");
+        g.nb = mom_blocks(n, R);
+    });
+    g.nb_max = mom_blocks(n, MOM_MAX0_R);
+    g.nn = (g.nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
+    return g;
+}
+
+// The scratch of a reduction: partials of one pass ([columns][workgroups], two levels), the closed trees on the device and where they
+// land on the host.  Grow-only; a capacity is zeroed before its block is replaced, so a failed allocation leaves a holder that
+// allocates again next time.
+struct mom_scratch {
+    mp_dev<double> buf[2];
+    mp_dev<double> res;
+    mp_pinned<double> host;
+    size_t cap[3] = {0, 0, 0};   // doubles in buf[0], in buf[1], and in res and host each
+    bool holds(size_t cols, const mom_grids& g, size_t n_res) const { return cols * g.nb <= cap[0] && cols * g.nn <= cap[1] && n_res <= cap[2]; }
+    // room for `cols` columns of g.nb partials each (the max pass's g.nb_max <= g.nb fit too) and for n_res results
+    hipError_t reserve(size_t cols, const mom_grids& g, size_t n_res) {
+        const size_t want[3] = {cols * (size_t)g.nb, cols * (size_t)g.nn, n_res};
+        for (int k = 0; k < 3; ++k) {
+            if (want[k] <= cap[k]) continue;
+            cap[k] = 0;
+            hipError_t e = k < 2 ? mp_hipMalloc(buf[k], want[k]) : mp_hipMalloc(res, want[k]);
+            if (e == hipSuccess && k == 2) e = mp_hipHostMalloc(host, want[k]);
+            if (e != hipSuccess) return e;
+            cap[k] = want[k];
+        }
+        return hipSuccess;
+    }
+};
+
+// Close the trees of `cols` columns of `nb` partials each ([cols][nb] in buf[0]) into dst[cols].  buf[0] holds cols * nb doubles, buf[1]
+// cols * ceil(nb / 1024).  At least one launch: a single partial goes through the tree as v + 0.  A grid has at most 65535 rows, so
+// the columns go in slices of that many, each closing inside its own part of the two buffers.
 template <class Op>
-static inline void mom_close(hipStream_t stream, double* const buf[2], unsigned long long nb, unsigned cols, double* dst) {
-    int cur = 0;
-    for (;;) {
-        const unsigned long long nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
-        hipLaunchKernelGGL(k_mom_tree<Op>, dim3((unsigned)nn, cols), dim3(MOM_THREADS), 0, stream, (const double*)buf[cur], nb, nn == 1 ? dst : buf[cur ^ 1], nn);
-        if (nn == 1) return;
-        nb = nn;
-        cur ^= 1;
+static inline void mom_close(hipStream_t stream, double* const buf[2], unsigned long long nb, unsigned long long cols, double* dst) {
+    const unsigned long long nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
+    for (unsigned long long c0 = 0; c0 < cols; c0 += 65535) {
+        double* const part[2] = {buf[0] + c0 * nb, buf[1] + c0 * nn};
+        const unsigned rows = (unsigned)std::min<unsigned long long>(65535, cols - c0);
+        int cur = 0;
+        for (unsigned long long in = nb, out = nn;; in = out, out = (out + MOM_TREE_RUN - 1) / MOM_TREE_RUN, cur ^= 1) {
+            hipLaunchKernelGGL(k_mom_tree<Op>, dim3((unsigned)out, rows), dim3(MOM_THREADS), 0, stream, (const double*)part[cur], in, out == 1 ? dst + c0 : part[cur ^ 1], out);
+            if (out == 1) break;
+        }
     }
 }

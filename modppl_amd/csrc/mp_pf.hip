@@ -440,31 +440,17 @@ struct mp_pf {
     size_t hist_slab_left = 0, hist_slab_next = 0;
     mp_dev<mp_hist_event> d_hist_events;   // device copy of the log for k_trajectories
     size_t d_hist_events_cap = 0;
-    // mp_pf_moments (mp_moments.h), allocated on first use: partials of one pass ([columns][workgroups], two levels), the closed trees
-    mp_dev<double> mom_buf[2];
-    mp_dev<double> mom_res;                // {m, A, S[d], mean[d], C[d (d + 1) / 2]}
-    mp_pinned<double> mom_host;            // ... and where they land on the host
-    // mp_pf_path_moments, sized on first use and grown with the time: the same three, for T * d columns (+ A), and the ancestor bitmap
-    mp_dev<double> path_buf[2];
-    mp_dev<double> path_res;               // {m, S[T][d], A, mean[T][d], V[T][d], distinct u64[T]}
-    mp_pinned<double> path_host;
-    mp_dev<uint32_t> path_bits;            // [T][ceil(n / 32)]
-    size_t path_cap_t = 0, path_bits_cap_t = 0;   // the T they hold
-    // mp_pf_forecast_moments, sized on first use and grown with the horizon: the same three for H * (dim_state + dim_obs) columns (+ A);
-    // mp_pf_forecast_paths: the device side of one chunk of the window ([chunk][H][dim_state], [chunk][H][dim_obs])
-    mp_dev<double> fc_buf[2];
-    mp_dev<double> fc_res;                 // {m, S[H][C], A, mean[H][C], V[H][C]}
-    mp_pinned<double> fc_host;
-    size_t fc_cap_h = 0;                   // the H they hold
-    mp_dev<double> fc_paths[2];            // states, observations
+    // The summary readouts (mp_pf_readouts.h).  ONE scratch for cloud moments, path moments, forecast moments and the quantiles' max pass
+    // and results: every one of these calls waits for the stream before it returns and a handle is single-threaded, so no call's
+    // scratch is live when the next begins.  Sized on first use, grown with the time, the horizon and the selectors.
+    mom_scratch scratch;
+    mp_dev<uint32_t> path_bits;            // mp_pf_path_moments: the ancestor bitmap [T][ceil(n / 32)]
+    size_t path_bits_cap_t = 0;            // (the T it holds)
+    mp_dev<double> fc_paths[2];            // mp_pf_forecast_paths: one chunk of the window, states [chunk][H][dim_state] and observations [chunk][H][dim_obs]
     size_t fc_paths_cap[2] = {0, 0};       // (doubles)
-    // mp_pf_quantiles / mp_pf_path_quantiles (mp_quantiles.h), allocated on first use and grown with the selectors (n_q * dim_state, per
-    // time step for the paths): the integer weights, the bins, {prefix, target, total} per selector, {m, Q[selectors]} and their host copy
-    mp_dev<u64> q_W;                       // [n]
-    mp_dev<u64> q_bins, q_st;              // [cap][256], [3][cap]
-    mp_dev<double> q_out;                  // [1 + cap]
-    mp_dev<double> q_max[2];               // partials of the max pass
-    mp_pinned<double> q_host;
+    // mp_pf_quantiles / mp_pf_path_quantiles (mp_quantiles.h), grown with the selectors (n_q * dim_state, per time step for the paths):
+    mp_dev<u64> q_W;                       // the integer weights [n]
+    mp_dev<u64> q_bins, q_st;              // the bins [cap][256], {prefix, target, total} per selector [3][cap]
     size_t q_cap = 0;                      // the selectors they hold
     // host-side filter state
     long long t = 0;  // Unfold steps taken (trace.args.0)
@@ -828,122 +814,9 @@ static int32_t ensure_rows(mp_pf* h) {
 
 static int32_t shard_scratch(mp_pf* h, int world, u64 cap);
 
-// mp_pf_moments: one level-0 launch of pass 1 (first moments) or 2 (centred second moments) for a state width D
-template <int D>
-static void launch_moments_pass(mp_pf* h, int pass, unsigned nb, const double* x, double* res) {
-    if (pass == 1)
-        hipLaunchKernelGGL((k_mom_pf1<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, x, (const double*)h->logw, (const double*)res,
-                           h->mom_buf[0].get());
-    else
-        hipLaunchKernelGGL((k_mom_pf2<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, x, (const double*)h->logw, (const double*)res,
-                           (const double*)(res + 1), res + 2 + D, h->mom_buf[0].get());
-}
-
-// the event log as the history kernels read it (k_trajectories, k_path_mom1/2), enqueued on the handle's stream; `ev` is the caller's
-// and stays alive until it has waited for the stream
-static int32_t upload_hist_events(mp_pf* h, std::vector<mp_hist_event>& ev) {
-    ev.resize(h->hist.size());
-    for (size_t e = 0; e < h->hist.size(); ++e) { ev[e].buf = h->hist[e].buf; ev[e].kind = h->hist[e].kind; ev[e].pad = 0; }
-    if (h->d_hist_events_cap < ev.size()) {
-        h->d_hist_events_cap = 0;
-        const size_t cap = std::max<size_t>(64, 2 * ev.size());
-        HIPCK(mp_hipMalloc(h->d_hist_events, cap));
-        h->d_hist_events_cap = cap;
-    }
-    HIPCK(hipMemcpyAsync(h->d_hist_events, ev.data(), sizeof(mp_hist_event) * ev.size(), hipMemcpyHostToDevice, h->stream));
-    return MP_OK;
-}
-
-// mp_pf_path_moments: the level-0 walk of pass 1 or 2 for a state width D; res = {m, S[T][D], A, mean[T][D], ...}
-template <int D>
-static void launch_path_pass(mp_pf* h, int pass, unsigned nb, int T, double* res, uint32_t* bitmap, u64 words) {
-    const mp_hist_event* ev = h->d_hist_events;
-    if (pass == 1)
-        hipLaunchKernelGGL((k_path_mom1<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, (int)h->hist.size(), T, ev, (const double*)h->logw,
-                           (const double*)res, h->path_buf[0].get(), bitmap, words);
-    else
-        hipLaunchKernelGGL((k_path_mom2<D>), dim3(nb), dim3(MOM_THREADS), 0, h->stream, h->n, (int)h->hist.size(), T, ev, (const double*)h->logw,
-                           (const double*)res, (const double*)(res + 1), res + 2 + (size_t)T * D, h->path_buf[0].get());
-}
-// mom_close for more columns than a grid has rows: slices of at most 65535 columns, each closing inside its own part of the two buffers
-static void path_close(hipStream_t stream, double* const buf[2], u64 nb, u64 cols, double* dst) {
-    const u64 nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
-    for (u64 c0 = 0; c0 < cols; c0 += 65535) {
-        double* const part[2] = {buf[0] + c0 * nb, buf[1] + c0 * nn};
-        mom_close<mom_add>(stream, part, nb, (unsigned)std::min<u64>(65535, cols - c0), dst + c0);
-    }
-}
-
-// mp_pf_quantiles / mp_pf_path_quantiles: the checks both share, the handle brought to a readable state (as mp_pf_moments does), room
-// for nsel_per_t * max(T, 1) selectors, then m = max lw -> q_out[0] and the integer weights -> q_W, enqueued on the handle's stream
-static int32_t quantiles_begin(mp_pf* h, const char* who, const double* qs, int32_t n_q, bool path, q_spec& spec, q_bufs& b, size_t& nsel) {
-    if (!q_make_spec(qs, n_q, spec)) return mp_fail(MP_ERR_INVALID_ARG, std::string(who) + ": n_q outside [1, 16], or a level that is NaN or outside [0, 1]");
-    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, std::string(who) + ": one shard of a larger world (n_global != n_particles); the quantiles of a sharded job need an all-reduce of the max and of the bins");
-    if (path && !(h->flags & MP_PF_RECORD_HISTORY)) return mp_fail(MP_ERR_STATE, std::string(who) + " needs a filter created with MP_PF_RECORD_HISTORY");
-    if (!h->initialised) return mp_fail(MP_ERR_STATE, std::string(who) + " before init_step");
-    const int d = h->ops->dim_state;
-    if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, std::string(who) + ": no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
-    HIPCK(hipSetDevice(h->device));
-    MPCK(materialize(h));
-    MPCK(ensure_x(h));
-    MPCK(ensure_lazy(h));
-    if (path) {
-        size_t n_step_events = 0;
-        for (const auto& e : h->hist) n_step_events += e.kind == 0;
-        if (n_step_events != (size_t)h->t) return mp_fail(MP_ERR_STATE, std::string(who) + ": the recorded history does not hold one state per step");
-    }
-    nsel = (size_t)n_q * d * (path ? (size_t)h->t : 1);
-    // every selector owns 2 KiB of bins, refilled on each pass: a call is held to Q_MAX_SEL of them (0.5 GiB) rather than left to hipMalloc
-    if (nsel > (size_t)Q_MAX_SEL) return mp_fail(MP_ERR_UNSUPPORTED, std::string(who) + ": time steps * n_q * dim_state exceeds " + std::to_string(Q_MAX_SEL) + " selectors; ask for fewer levels per call");
-    const u64 nb_max = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);
-    if (!h->q_W) {
-        HIPCK(mp_hipMalloc(h->q_max[0], nb_max));
-        HIPCK(mp_hipMalloc(h->q_max[1], (nb_max + MOM_TREE_RUN - 1) / MOM_TREE_RUN));
-        HIPCK(mp_hipMalloc(h->q_W, h->n));
-    }
-    if (h->q_cap < nsel) {
-        const size_t cap = std::min<size_t>((size_t)Q_MAX_SEL, std::max<size_t>((size_t)Q_MAX_Q * MOM_MAX_DIM, 2 * nsel));
-        h->q_cap = 0;
-        HIPCK(mp_hipMalloc(h->q_bins, cap * Q_BINS));
-        HIPCK(mp_hipMalloc(h->q_st, 3 * cap));
-        HIPCK(mp_hipMalloc(h->q_out, 1 + cap));
-        HIPCK(mp_hipHostMalloc(h->q_host, 1 + cap));
-        h->q_cap = cap;
-    }
-    b = q_bufs{h->q_bins.get(), h->q_st.get(), h->q_st.get() + h->q_cap, h->q_st.get() + 2 * h->q_cap, h->q_out.get() + 1};
-    if (nsel == 0) return MP_OK;   // (a history filter at time 0)
-    double* const buf[2] = {h->q_max[0].get(), h->q_max[1].get()};
-    hipLaunchKernelGGL(k_mom_max0, dim3((unsigned)nb_max), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->logw, buf[0]);
-    mom_close<mom_max>(h->stream, buf, nb_max, 1, h->q_out.get());
-    hipLaunchKernelGGL(k_q_weights, dim3((unsigned)((h->n + Q_THREADS - 1) / Q_THREADS)), dim3(Q_THREADS), 0, h->stream, h->n, (const double*)h->logw,
-                       (const double*)h->q_out.get(), q_scale(h->n), h->q_W.get());
-    return check_launch("mp_pf quantile weights");
-}
-// ... and the end: {m, Q[nsel]} to the host, the one wait, the statuses m decides
-static int32_t quantiles_end(mp_pf* h, hipError_t e1, size_t nsel, double* out) {
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(h->q_host, h->q_out, sizeof(double) * (1 + nsel), hipMemcpyDeviceToHost, h->stream);
-    if (e1 != hipSuccess) { (void)hipStreamSynchronize(h->stream); return mp_fail(MP_ERR_HIP, std::string("quantiles: ") + hipGetErrorString(e1)); }
-    HIPCK(stream_wait(h->stream));
-    const double* r = h->q_host;
-    if (r[0] == -MP_INF) return mp_fail_degenerate();
-    // (a NaN max: every weight is 0, every selector was clamped and holds NaN already)
-    memcpy(out, r + 1, sizeof(double) * nsel);
-    return MP_OK;
-}
-template <int D>
-static void launch_quantiles_hist(mp_pf* h, int pass, int nq, const q_bufs& b) {
-    const unsigned nb = (unsigned)((h->n + (u64)Q_THREADS * Q_ROWS - 1) / ((u64)Q_THREADS * Q_ROWS));
-    constexpr int QC = Q_SEL_CHUNK / D;
-    hipLaunchKernelGGL((k_q_hist_pf<D>), dim3(nb, (unsigned)((nq + QC - 1) / QC)), dim3(Q_THREADS), 0, h->stream, h->n, (const double*)h->x[h->cur],
-                       (const u64*)h->q_W.get(), pass, nq, b);
-}
-template <int D>
-static void launch_path_quantiles_hist(mp_pf* h, int pass, int nq, int Q, const q_bufs& b) {
-    constexpr int R = mom_run<D>::R, QC = Q_SEL_CHUNK / D;
-    const unsigned nb = (unsigned)((h->n + (u64)Q_THREADS * R - 1) / ((u64)Q_THREADS * R));
-    hipLaunchKernelGGL((k_q_hist_path<D>), dim3(nb, (unsigned)((nq + QC - 1) / QC)), dim3(Q_THREADS), 0, h->stream, h->n, (int)h->hist.size(), (int)h->t,
-                       (const mp_hist_event*)h->d_hist_events, (const u64*)h->q_W.get(), pass, nq, Q, b);
-}
+// the summary readouts and the trajectories: mp_pf_moments, _path_moments, _quantiles, _path_quantiles, _forecast_paths, _forecast_moments,
+// _read_trajectories (host code: one preamble, one scratch, one ending)
+#include "mp_pf_readouts.h"
 
 extern "C" {
 
@@ -1349,63 +1222,6 @@ int32_t mp_pf_read_parents(mp_pf* h, uint32_t* out) {
     }
     HIPCK(hipMemcpyAsync(out, h->parent, sizeof(uint32_t) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    return MP_OK;
-}
-
-// Weighted mean and covariance of the particle cloud, reduced on the device: replaces the host-side reduction a caller of the reference
-// writes over its public `traces` / `log_weights` fields (particle_filter.rs:13-20) — here mp_pf_read_state + mp_pf_read_log_weights
-// and a loop.  Definition (the tree sum, relative to the global max log-weight): mp_moments.h, DESIGN.md section 4.
-// All launches are enqueued before the one wait, so a cloud whose log-weights are all -inf still pays for every pass (its weights are
-// selected to 0 and nothing is returned but the status): looking at m after the max pass would cost every healthy call a second wait.
-int32_t mp_pf_moments(mp_pf* h, double* mean_out, double* cov_out) {
-    if (!h || !mean_out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
-    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_moments: one shard of a larger world (n_global != n_particles); the moments of a sharded job need an all-reduce of the max and an all-gather of the partials");
-    if (!h->initialised) return mp_fail(MP_ERR_STATE, "moments before init_step");
-    const int d = h->ops->dim_state;
-    if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_moments: no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
-    HIPCK(hipSetDevice(h->device));
-    MPCK(materialize(h));
-    MPCK(ensure_x(h));
-    MPCK(ensure_lazy(h));
-    const int R = d <= 4 ? 8 : 4;   // mom_run<D>::R
-    const int npairs = d * (d + 1) / 2;
-    const u64 nb = (h->n + (u64)MOM_THREADS * R - 1) / ((u64)MOM_THREADS * R);          // workgroups of the two moment passes
-    const u64 nb_max = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);      // ... and of the max pass (<= nb)
-    const size_t n_res = 2 + 2 * (size_t)d + npairs;
-    if (!h->mom_res) {
-        const size_t cols = (size_t)std::max(d + 1, npairs);
-        HIPCK(mp_hipMalloc(h->mom_buf[0], cols * nb));
-        HIPCK(mp_hipMalloc(h->mom_buf[1], cols * ((nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN)));
-        HIPCK(mp_hipHostMalloc(h->mom_host, n_res));
-        HIPCK(mp_hipMalloc(h->mom_res, n_res));
-    }
-    double* const buf[2] = {h->mom_buf[0].get(), h->mom_buf[1].get()};
-    double* res = h->mom_res;
-    const double* x = h->x[h->cur];
-    hipLaunchKernelGGL(k_mom_max0, dim3((unsigned)nb_max), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->logw, buf[0]);
-    mom_close<mom_max>(h->stream, buf, nb_max, 1, res);
-    for (int pass = 1; pass <= (cov_out ? 2 : 1); ++pass) {
-        switch (d) {
-        case 1: launch_moments_pass<1>(h, pass, (unsigned)nb, x, res); break;
-        case 2: launch_moments_pass<2>(h, pass, (unsigned)nb, x, res); break;
-        case 4: launch_moments_pass<4>(h, pass, (unsigned)nb, x, res); break;
-        default: launch_moments_pass<16>(h, pass, (unsigned)nb, x, res); break;
-        }
-        mom_close<mom_add>(h->stream, buf, nb, pass == 1 ? (unsigned)(d + 1) : (unsigned)npairs, pass == 1 ? res + 1 : res + 2 + 2 * d);
-    }
-    MPCK(check_launch("mp_pf_moments kernels"));
-    HIPCK(hipMemcpyAsync(h->mom_host, res, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(stream_wait(h->stream));
-    const double* r = h->mom_host;
-    if (r[0] == -MP_INF) return mp_fail_degenerate();
-    const double A = r[1];
-    // without a covariance pass nobody has formed the means on the device: the same IEEE division here
-    for (int j = 0; j < d; ++j) mean_out[j] = cov_out ? r[2 + d + j] : r[2 + j] / A;
-    if (cov_out) {
-        const double* C = r + 2 + 2 * d;
-        for (int j = 0; j < d; ++j)
-            for (int k = 0; k <= j; ++k) cov_out[j * d + k] = cov_out[k * d + j] = C[j * (j + 1) / 2 + k] / A;
-    }
     return MP_OK;
 }
 
@@ -2021,275 +1837,6 @@ int32_t mp_pf_shard_query_packed(mp_pf* h, const uint64_t* d_tiles_all, int32_t 
     MPCK(fetch_scalars(h));
     if (log_ml) *log_ml = h->h_scal->lml_fresh;
     if (ess) *ess = h->h_scal->ess_fresh;
-    return MP_OK;
-}
-
-int32_t mp_pf_read_trajectories(mp_pf* h, uint64_t first, uint64_t count, double* out, int32_t* t_steps) {
-    if (!h || !out || !t_steps) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
-    if (!(h->flags & MP_PF_RECORD_HISTORY)) return mp_fail(MP_ERR_STATE, "read_trajectory needs a filter created with MP_PF_RECORD_HISTORY");
-    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, "read_trajectory: ancestors of a sharded filter live on other ranks");
-    if (count == 0 || first >= h->n || count > h->n - first) return mp_fail(MP_ERR_INVALID_ARG, "particle range out of bounds");
-    HIPCK(hipSetDevice(h->device));
-    const int d = h->ops->dim_state;
-    const int T = (int)h->t;
-    *t_steps = (int32_t)h->t;
-    if (T == 0) return MP_OK;
-    std::vector<mp_hist_event> ev;
-    MPCK(upload_hist_events(h, ev));
-    mp_dev<double> d_out;
-    const size_t bytes = sizeof(double) * (size_t)count * (size_t)T * (size_t)d;
-    HIPCK(mp_hipMalloc(d_out, (size_t)count * (size_t)T * (size_t)d));
-    hipLaunchKernelGGL(k_trajectories, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, (u64)first, (u64)count, d, T, (int)ev.size(),
-                       (const mp_hist_event*)h->d_hist_events, d_out.get());
-    hipError_t e1 = hipGetLastError();
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(h->stream);   // (ev / d_out stay alive until here)
-    if (e1 != hipSuccess) return mp_fail(MP_ERR_HIP, std::string("mp_pf_read_trajectories: ") + hipGetErrorString(e1));
-    return MP_OK;
-}
-
-int32_t mp_pf_read_trajectory(mp_pf* h, uint64_t i, double* out, int32_t* t_steps) {
-    return mp_pf_read_trajectories(h, i, 1, out, t_steps);
-}
-
-// Smoothed mean and variance per time step over the recorded ancestry, and the number of distinct ancestors per step, reduced on the
-// device: replaces walking `traces[i].retv` of every particle (particle_filter.rs:13; tests/smc.rs:67) — here mp_pf_read_trajectories,
-// n * T * d doubles over the link — and a host loop.  Definition: mp_moments.h, DESIGN.md section 4, "Path moments".
-// As in mp_pf_moments every launch is enqueued before the one wait.
-int32_t mp_pf_path_moments(mp_pf* h, double* mean_out, double* var_out, uint64_t* distinct_out, int32_t* t_steps) {
-    if (!h || !mean_out || !t_steps) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
-    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_path_moments: ancestors of a sharded filter live on other ranks");
-    if (!(h->flags & MP_PF_RECORD_HISTORY)) return mp_fail(MP_ERR_STATE, "path_moments needs a filter created with MP_PF_RECORD_HISTORY");
-    if (!h->initialised) return mp_fail(MP_ERR_STATE, "path_moments before init_step");
-    const int d = h->ops->dim_state;
-    if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_path_moments: no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
-    HIPCK(hipSetDevice(h->device));
-    MPCK(materialize(h));
-    MPCK(ensure_x(h));
-    MPCK(ensure_lazy(h));
-    const int T = (int)h->t;
-    *t_steps = (int32_t)h->t;
-    if (T == 0) return MP_OK;
-    size_t n_step_events = 0;
-    for (const auto& e : h->hist) n_step_events += e.kind == 0;
-    if (n_step_events != (size_t)T) return mp_fail(MP_ERR_STATE, "mp_pf_path_moments: the recorded history does not hold one state per step");
-    const int R = d <= 4 ? 8 : 4;   // mom_run<D>::R
-    const u64 nb = (h->n + (u64)MOM_THREADS * R - 1) / ((u64)MOM_THREADS * R);
-    const u64 nb_max = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);   // (<= nb)
-    const u64 nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
-    const size_t TD = (size_t)T * d;
-    const size_t n_res = 2 + 3 * TD + (size_t)T;
-    if (h->path_cap_t < (size_t)T) {
-        const size_t cap = std::max<size_t>(16, 2 * (size_t)T), cols = cap * d + 1;
-        h->path_cap_t = 0;
-        HIPCK(mp_hipMalloc(h->path_buf[0], cols * nb));
-        HIPCK(mp_hipMalloc(h->path_buf[1], cols * nn));
-        HIPCK(mp_hipHostMalloc(h->path_host, 2 + 3 * cap * d + cap));
-        HIPCK(mp_hipMalloc(h->path_res, 2 + 3 * cap * d + cap));
-        h->path_cap_t = cap;
-    }
-    const u64 words = (h->n + 31) / 32;
-    if (distinct_out && h->path_bits_cap_t < (size_t)T) {
-        const size_t cap = std::max<size_t>(16, 2 * (size_t)T);
-        h->path_bits_cap_t = 0;
-        HIPCK(mp_hipMalloc(h->path_bits, cap * words));
-        h->path_bits_cap_t = cap;
-    }
-    std::vector<mp_hist_event> ev;
-    MPCK(upload_hist_events(h, ev));
-    double* const buf[2] = {h->path_buf[0].get(), h->path_buf[1].get()};
-    double* res = h->path_res;
-    unsigned long long* d_distinct = reinterpret_cast<unsigned long long*>(res + 2 + 3 * TD);
-    uint32_t* bitmap = distinct_out ? h->path_bits.get() : nullptr;
-    if (bitmap) HIPCK(hipMemsetAsync(bitmap, 0, sizeof(uint32_t) * (size_t)T * words, h->stream));
-    hipLaunchKernelGGL(k_mom_max0, dim3((unsigned)nb_max), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->logw, buf[0]);
-    mom_close<mom_max>(h->stream, buf, nb_max, 1, res);
-    for (int pass = 1; pass <= (var_out ? 2 : 1); ++pass) {
-        switch (d) {
-        case 1: launch_path_pass<1>(h, pass, (unsigned)nb, T, res, bitmap, words); break;
-        case 2: launch_path_pass<2>(h, pass, (unsigned)nb, T, res, bitmap, words); break;
-        case 4: launch_path_pass<4>(h, pass, (unsigned)nb, T, res, bitmap, words); break;
-        default: launch_path_pass<16>(h, pass, (unsigned)nb, T, res, bitmap, words); break;
-        }
-        path_close(h->stream, buf, nb, pass == 1 ? TD + 1 : TD, pass == 1 ? res + 1 : res + 2 + 2 * TD);
-    }
-    if (bitmap) hipLaunchKernelGGL(k_path_distinct, dim3((unsigned)T), dim3(MOM_THREADS), 0, h->stream, (const uint32_t*)bitmap, words, d_distinct);
-    hipError_t e1 = hipGetLastError();
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(h->path_host, res, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream);
-    if (e1 != hipSuccess) { (void)hipStreamSynchronize(h->stream); return mp_fail(MP_ERR_HIP, std::string("mp_pf_path_moments: ") + hipGetErrorString(e1)); }   // (ev stays alive until the stream is idle)
-    MPCK(stream_wait(h->stream));
-    const double* r = h->path_host;
-    if (r[0] == -MP_INF) return mp_fail_degenerate();
-    const double A = r[1 + TD];
-    // without a variance pass nobody has formed the means on the device: the same IEEE division here
-    for (size_t c = 0; c < TD; ++c) mean_out[c] = var_out ? r[2 + TD + c] : r[1 + c] / A;
-    if (var_out)
-        for (size_t c = 0; c < TD; ++c) var_out[c] = r[2 + 2 * TD + c] / A;
-    if (distinct_out) memcpy(distinct_out, r + 2 + 3 * TD, sizeof(uint64_t) * (size_t)T);
-    return MP_OK;
-}
-
-// Weighted quantiles of every state component of the cloud, selected on the device: replaces sorting what a caller of the reference
-// collects from its public `traces` / `log_weights` fields (particle_filter.rs:13-20) — here mp_pf_read_state + mp_pf_read_log_weights
-// and a host sort.  Definition (integers only: the weighted inverted CDF over order-preserving keys): mp_quantiles.h, DESIGN.md
-// section 4, "Quantiles".  As in mp_pf_moments every launch is enqueued before the one wait, and m is looked at once, at the end.
-int32_t mp_pf_quantiles(mp_pf* h, const double* qs, int32_t n_q, double* out) {
-    if (!h || !qs || !out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
-    q_spec spec;
-    q_bufs b;
-    size_t nsel = 0;
-    MPCK(quantiles_begin(h, "mp_pf_quantiles", qs, n_q, false, spec, b, nsel));
-    const int d = h->ops->dim_state;
-    const hipError_t e1 = q_select(h->stream, b, nsel, n_q, d, spec, [&](int pass, int nq, const q_bufs& bb) {
-        switch (d) {
-        case 1: launch_quantiles_hist<1>(h, pass, nq, bb); break;
-        case 2: launch_quantiles_hist<2>(h, pass, nq, bb); break;
-        case 4: launch_quantiles_hist<4>(h, pass, nq, bb); break;
-        default: launch_quantiles_hist<16>(h, pass, nq, bb); break;
-        }
-    });
-    return quantiles_end(h, e1, nsel, out);
-}
-
-// Weighted quantiles of the state at EVERY time step over the recorded ancestry (the bands of a fan chart), selected on the device:
-// replaces walking `traces[i].retv` of every particle (particle_filter.rs:13; tests/smc.rs:67) and sorting per step on the host — here
-// mp_pf_read_trajectories, n * T * d doubles over the link.  The weights of mp_pf_quantiles over v_ij(t) = x_t[anc_i(t)]; the walk of
-// mp_pf_path_moments, once per pass.  Definition: mp_quantiles.h, DESIGN.md section 4, "Quantiles".
-int32_t mp_pf_path_quantiles(mp_pf* h, const double* qs, int32_t n_q, double* out, int32_t* t_out) {
-    if (!h || !qs || !out || !t_out) return mp_fail(MP_ERR_INVALID_ARG, "null argument");
-    q_spec spec;
-    q_bufs b;
-    size_t nsel = 0;
-    MPCK(quantiles_begin(h, "mp_pf_path_quantiles", qs, n_q, true, spec, b, nsel));
-    *t_out = (int32_t)h->t;
-    if (h->t == 0) return MP_OK;
-    const int d = h->ops->dim_state;
-    std::vector<mp_hist_event> ev;   // (stays alive until the stream is idle: quantiles_end waits on every path)
-    const int32_t up = upload_hist_events(h, ev);
-    if (up != MP_OK) { (void)hipStreamSynchronize(h->stream); return up; }   // (a copy out of ev may be in flight: wait, then the status as it came)
-    const hipError_t e1 = q_select(h->stream, b, nsel, n_q, d, spec, [&](int pass, int nq, const q_bufs& bb) {
-        switch (d) {
-        case 1: launch_path_quantiles_hist<1>(h, pass, nq, n_q, bb); break;
-        case 2: launch_path_quantiles_hist<2>(h, pass, nq, n_q, bb); break;
-        case 4: launch_path_quantiles_hist<4>(h, pass, nq, n_q, bb); break;
-        default: launch_path_quantiles_hist<16>(h, pass, nq, n_q, bb); break;
-        }
-    });
-    return quantiles_end(h, e1, nsel, out);
-}
-
-// The forecast (mp_forecast.h; DESIGN.md section 4, "Forecast"): DynUnfold::update with ArgDiff::Extend and EMPTY constraints for the new
-// steps (modppl/src/modeling/dynunfold.rs:66-100) — every site of the next `horizon` kernel calls drawn, from each slot's own state,
-// with the Philox counters the next steps would use.  Both calls bring the handle to a readable state as mp_pf_moments does and change
-// nothing the filter computes afterwards: no state, weight, parent, counter, time or history event.
-static int32_t forecast_begin(mp_pf* h, const char* who, int32_t horizon, mp_forecast_args& f) {
-    if (!h) return mp_fail(MP_ERR_INVALID_ARG, "null handle");
-    if (h->model_kind == MP_MODEL_HMM) return mp_fail(MP_ERR_UNSUPPORTED, "the reference's HMM has no simulate (tests/hmm/model.rs: unimplemented)");
-    if (!h->initialised) return mp_fail(MP_ERR_STATE, std::string(who) + " before init_step");
-    if (horizon < 1) return mp_fail(MP_ERR_INVALID_ARG, std::string(who) + ": horizon must be at least 1");
-    f.n = h->n; f.slot_offset = h->slot_offset;
-    f.k0 = (uint32_t)h->seed; f.k1 = (uint32_t)(h->seed >> 32);
-    f.t = h->t;
-    f.horizon = horizon;
-    return MP_OK;
-}
-// a grow-only device buffer of at least `want` doubles
-static int32_t fc_grow(mp_dev<double>& buf, size_t& cap, size_t want) {
-    if (cap >= want) return MP_OK;
-    cap = 0;
-    HIPCK(mp_hipMalloc(buf, want));
-    cap = want;
-    return MP_OK;
-}
-
-int32_t mp_pf_forecast_paths(mp_pf* h, int32_t horizon, uint64_t first, uint64_t count, double* states_out, double* obs_out) {
-    mp_forecast_args f;
-    MPCK(forecast_begin(h, "forecast_paths", horizon, f));
-    if (!states_out && !obs_out) return mp_fail(MP_ERR_INVALID_ARG, "forecast_paths: every output is null");
-    if (first > h->n || count > h->n - first) return mp_fail(MP_ERR_INVALID_ARG, "forecast_paths: first + count exceeds the number of particles");
-    HIPCK(hipSetDevice(h->device));
-    MPCK(materialize(h));
-    MPCK(ensure_x(h));
-    MPCK(ensure_lazy(h));
-    f.x = h->x[h->cur];
-    const size_t D = (size_t)h->ops->dim_state, DO = (size_t)h->ops->dim_obs, H = (size_t)horizon;
-    // slots per launch: 2^22 doubles of states + observations on the device at a time, but never fewer than 2^16 slots (a launch that
-    // fills the device), whatever the window and the horizon
-    const u64 chunk = std::max<u64>(1, std::min<u64>(count, std::max<u64>((u64)1 << 16, ((u64)1 << 22) / (H * (D + DO)))));
-    if (states_out) MPCK(fc_grow(h->fc_paths[0], h->fc_paths_cap[0], (size_t)chunk * H * D));
-    if (obs_out) MPCK(fc_grow(h->fc_paths[1], h->fc_paths_cap[1], (size_t)chunk * H * DO));
-    double* dx = states_out ? h->fc_paths[0].get() : nullptr;
-    double* dy = obs_out ? h->fc_paths[1].get() : nullptr;
-    hipError_t e = hipSuccess;
-    for (u64 c0 = 0; c0 < count && e == hipSuccess; c0 += chunk) {
-        const u64 cn = std::min<u64>(chunk, count - c0);
-        h->ops->forecast_paths(f, first + c0, cn, dx, dy, h->stream);
-        e = hipGetLastError();
-        if (e == hipSuccess && dx) e = hipMemcpyAsync(states_out + (size_t)c0 * H * D, dx, sizeof(double) * (size_t)cn * H * D, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess && dy) e = hipMemcpyAsync(obs_out + (size_t)c0 * H * DO, dy, sizeof(double) * (size_t)cn * H * DO, hipMemcpyDeviceToHost, h->stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return mp_fail(MP_ERR_HIP, std::string("mp_pf_forecast_paths: ") + hipGetErrorString(e));
-    return MP_OK;
-}
-
-// As in mp_pf_moments every launch is enqueued before the one wait.  The kernels reduce the state and the observation columns alike
-// (Simulate mode draws the observations anyway); what the caller did not ask for is not copied out.
-int32_t mp_pf_forecast_moments(mp_pf* h, int32_t horizon, double* state_mean_out, double* state_var_out, double* obs_mean_out, double* obs_var_out) {
-    mp_forecast_args f;
-    MPCK(forecast_begin(h, "forecast_moments", horizon, f));
-    if (!state_mean_out && !state_var_out && !obs_mean_out && !obs_var_out) return mp_fail(MP_ERR_INVALID_ARG, "forecast_moments: every output is null");
-    if (h->sharded) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_forecast_moments: one shard of a larger world (n_global != n_particles); the moments of a sharded job need an all-reduce of the max and an all-gather of the partials");
-    const int d = h->ops->dim_state, dobs = h->ops->dim_obs;
-    if (d != 1 && d != 2 && d != 4 && d != 16) return mp_fail(MP_ERR_UNSUPPORTED, "mp_pf_forecast_moments: no kernel for this dim_state (the compiled models have 1, 2, 4 or 16)");
-    HIPCK(hipSetDevice(h->device));
-    MPCK(materialize(h));
-    MPCK(ensure_x(h));
-    MPCK(ensure_lazy(h));
-    f.x = h->x[h->cur];
-    const int R = d <= 4 ? 8 : 4;   // mom_run<D>::R
-    const size_t C = (size_t)(d + dobs), H = (size_t)horizon, HC = H * C;
-    const u64 nb = (h->n + (u64)MOM_THREADS * R - 1) / ((u64)MOM_THREADS * R);
-    const u64 nb_max = (h->n + (u64)MOM_THREADS * 8 - 1) / ((u64)MOM_THREADS * 8);   // (<= nb)
-    const u64 nn = (nb + MOM_TREE_RUN - 1) / MOM_TREE_RUN;
-    const size_t n_res = 2 + 3 * HC;
-    if (h->fc_cap_h < H) {
-        const size_t cap = std::max<size_t>(16, 2 * H), cols = cap * C + 1;
-        h->fc_cap_h = 0;
-        HIPCK(mp_hipMalloc(h->fc_buf[0], cols * nb));
-        HIPCK(mp_hipMalloc(h->fc_buf[1], cols * nn));
-        HIPCK(mp_hipHostMalloc(h->fc_host, 2 + 3 * cap * C));
-        HIPCK(mp_hipMalloc(h->fc_res, 2 + 3 * cap * C));
-        h->fc_cap_h = cap;
-    }
-    double* const buf[2] = {h->fc_buf[0].get(), h->fc_buf[1].get()};
-    double* res = h->fc_res;
-    const bool want_var = state_var_out || obs_var_out;
-    hipLaunchKernelGGL(k_mom_max0, dim3((unsigned)nb_max), dim3(MOM_THREADS), 0, h->stream, h->n, (const double*)h->logw, buf[0]);
-    mom_close<mom_max>(h->stream, buf, nb_max, 1, res);
-    for (int pass = 1; pass <= (want_var ? 2 : 1); ++pass) {
-        h->ops->forecast_moments(f, pass, (unsigned)nb, h->logw, res, buf[0], h->stream);
-        path_close(h->stream, buf, nb, pass == 1 ? HC + 1 : HC, pass == 1 ? res + 1 : res + 2 + 2 * HC);
-    }
-    MPCK(check_launch("mp_pf_forecast_moments kernels"));
-    HIPCK(hipMemcpyAsync(h->fc_host, res, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(stream_wait(h->stream));
-    const double* r = h->fc_host;
-    if (r[0] == -MP_INF) return mp_fail_degenerate();
-    const double A = r[1 + HC];
-    // without a variance pass nobody has formed the means on the device: the same IEEE division here
-    for (size_t k = 0; k < H; ++k)
-        for (size_t c = 0; c < C; ++c) {
-            const size_t col = k * C + c;
-            const double mean = want_var ? r[2 + HC + col] : r[1 + col] / A;
-            const bool is_state = c < (size_t)d;
-            double* mo = is_state ? state_mean_out : obs_mean_out;
-            double* vo = is_state ? state_var_out : obs_var_out;
-            const size_t o = is_state ? k * d + c : k * dobs + (c - d);
-            if (mo) mo[o] = mean;
-            if (vo) vo[o] = r[2 + 2 * HC + col] / A;
-        }
     return MP_OK;
 }
 
